@@ -32,7 +32,21 @@ with their status; every rank owns 65,536 agents with global ids (no
 collective in the step), the timing is max-over-ranks, and the collector
 leg all-gathers its trajectory buffers over RCCL at the rollout boundary.
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--fuse F]
+A plain run (``--gpus N --steps K --warmup W``) does the headline window
+alone: set up, warm up, time the K steps, print the result line.  ``--full``
+adds every other measurement to the line: the HIP-event re-run of the window
+(``roofline``), ``episode_window``, ``same_window_other_fuse``, the one-step
+call, simpleEnv, the room-set legs, the collector and learner legs and the
+CPU baselines; each keeps its own switch (``--simple 0``, ``--collector
+none``, ...), which selects among them under ``--full``.
+
+``--dump-outputs DIR`` writes what the last timed step of the headline window
+returned -- obs [N, 80], reward, terminated, truncated [N], as float32 -- to
+``DIR/<name>.npy`` (``<name>_rank<r>.npy`` per rank when N > 1).  The inputs
+are seeded, so two builds run with the same arguments can be compared array
+for array.
+
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--fuse F] [--full] [--dump-outputs DIR]
 """
 from __future__ import annotations
 
@@ -51,6 +65,7 @@ sys.path.insert(0, str(REPO / "3d-navigation-reinforcement-learning_amd"))
 METRIC = "env-steps/sec at 65536 parallel agents, 32×32×8 room, 1/2/4/8 MI355X"
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: 8.0 TB/s spec
 EPISODE_WINDOW = 5408   # one whole 5,400-step episode of the 32x32x8 box, in F=16 launches
+DUMP_BUDGET = 64_000_000   # --dump-outputs writes at most this many bytes
 
 
 def algorithmic_bytes_per_step(L: int) -> int:
@@ -95,7 +110,19 @@ def parse(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="launch/rendezvous rehearsal without a GPU: ranks init gloo, time a barrier, print the line")
     ap.add_argument("--json-out", default=None)
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beside the headline window (roofline re-run, episode window, "
+                         "other launch sizes, simpleEnv, room sets, collector and learner legs, CPU baselines); "
+                         "their own switches select among them")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs (obs, reward, terminated, truncated) as DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if not args.full:
+        # a plain run is the headline window alone
+        args.episode_window = args.fuse_check = args.single_step_check = args.simple = 0
+        args.room_sets = args.collector = "none"
+        args.cpu_seconds = 0.0
+    return args
 
 
 # ---------------------------------------------------------------- launch
@@ -458,6 +485,26 @@ def time_window(torch, dist, dev, world, env, N, F, warmup, steps, policy_seed=4
     return elapsed, kern_ms, timed, out
 
 
+def dump_outputs(dirpath, out, k_last, rank, world):
+    """``--dump-outputs``: the arrays the last timed step returned (row
+    ``k_last - 1`` of the last launch's rollout chunk), float32, one .npy per
+    array.  When all agents would exceed DUMP_BUDGET, a fixed seeded sample of
+    agents (sorted ids, the same in every run) is written instead."""
+    import numpy as np
+    d = Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    row = k_last - 1
+    arrays = {"obs": out.obs[row], "reward": out.reward[row], "terminated": out.terminated[row],
+              "truncated": out.truncated[row]}
+    N = out.obs.shape[1]
+    keep = (DUMP_BUDGET - 4096) // (4 * (out.obs.shape[2] + 3))   # 4096: the .npy headers
+    idx = np.sort(np.random.default_rng(0).choice(N, size=keep, replace=False)) if N > keep else None
+    suffix = "" if world == 1 else f"_rank{rank}"
+    for name, t in arrays.items():
+        a = t.float().cpu().numpy()
+        np.save(d / f"{name}{suffix}.npy", a if idx is None else a[idx])
+
+
 def roofline_block(bstep, N, F, steps, timed, kern_ms, traffic_rec, kernel_label):
     """Roofline of the dominant kernel over ONE window: algorithmic bytes of
     the window's env-steps / the window's summed launch time.  Per-launch
@@ -578,14 +625,18 @@ def main():
     label = env.kernel_label(F)
     elapsed, _, timed, out = time_window(torch, dist, dev, world, env, N, F, args.warmup, args.steps, events=False)
     assert torch.isfinite(out.obs).all().item()   # the trajectory buffer holds real observations
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, timed[-1], rank, world)
     env.close()
     del env, out
-    env = make_env()
-    ev_el, kern_ms, _, _ = time_window(torch, dist, dev, world, env, N, F, args.warmup, args.steps)
-    env.close()
-    del env
-    roof = roofline_block(bstep, N, F, args.steps, timed, kern_ms,
-                          traffic_for(W, D, H, args.L, N, F, args.warmup, args.steps), label)
+    roof = ev_el = None
+    if args.full:
+        env = make_env()
+        ev_el, kern_ms, _, _ = time_window(torch, dist, dev, world, env, N, F, args.warmup, args.steps)
+        env.close()
+        del env
+        roof = roofline_block(bstep, N, F, args.steps, timed, kern_ms,
+                              traffic_for(W, D, H, args.L, N, F, args.warmup, args.steps), label)
     value = N * world * args.steps / elapsed
     # every agent starts at t=0 and a random-policy episode truncates at the
     # room's free-cell count: an auto-reset is inside the
@@ -702,12 +753,15 @@ def main():
                        "steps_per_launch": F,
                        "window": f"fresh env, {args.warmup} untimed steps, then exactly {args.steps} timed steps "
                                  f"in {len(timed)} launches (episode steps {args.warmup + 1}-"
-                                 f"{args.warmup + args.steps}); roofline and traffic from the same launches of an "
-                                 f"identical re-run of the window timed with HIP events "
-                                 f"(wall {round(ev_el * 1e3 / args.steps, 5)} ms per step with the events)",
+                                 f"{args.warmup + args.steps})"
+                                 + (f"; roofline and traffic from the same launches of an "
+                                    f"identical re-run of the window timed with HIP events "
+                                    f"(wall {round(ev_el * 1e3 / args.steps, 5)} ms per step with the events)"
+                                    if args.full else ""),
                        "parallelism": f"agent-sharded x{world} (no collective in the step)"},
-            "roofline": roof,
         }
+        if roof is not None:
+            rec["roofline"] = roof
         if episode is not None:
             rec["episode_window"] = episode
         if fuse_alt is not None:

@@ -19,5 +19,5 @@ soft() { [ "$1" -eq 0 ] || [ "$1" -eq 1 ]; }
 STEPS=${STEPS:-smoke,tests,bench}
 if [[ $STEPS == *smoke* ]]; then run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"; rc=$?; soft $rc || exit $rc; fi
 if [[ $STEPS == *tests* ]]; then run pytest_gpu 1100 python -m pytest tests -m gpu -q ${PYTEST_ARGS:-}; rc=$?; soft $rc || exit $rc; fi
-if [[ $STEPS == *bench* ]]; then run bench 600 python bench.py ${BENCH_ARGS:-}; rc=$?; soft $rc || exit $rc; fi
+if [[ $STEPS == *bench* ]]; then run bench 600 python bench.py --full ${BENCH_ARGS:-}; rc=$?; soft $rc || exit $rc; fi
 exit 0

@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 TAG=${TAG:-coll}
-COMMON="--learner-batch 0 --simple 0 --episode-window 0 --fuse-check 0 --single-step-check 0 --cpu-seconds 0 --steps 16 --warmup 4"
+COMMON="--full --learner-batch 0 --simple 0 --episode-window 0 --fuse-check 0 --single-step-check 0 --cpu-seconds 0 --steps 16 --warmup 4"
 timeout -k 10 300 python bench.py --collector lstm,mlp --collector-bf16 1 $COMMON > gpurun_out/${TAG}_bench.json 2> gpurun_out/${TAG}_bench.err || exit $?
 python - "$TAG" <<'PY'
 import json, sys

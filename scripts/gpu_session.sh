@@ -10,6 +10,8 @@ TAG=${TAG:-s}
 run() {
   local name=$1 t=$2; shift 2
   [[ ",$STEPS," == *",$name,"* ]] || return 0
+  # these steps end in bench.py arguments and measure legs that bench.py runs only under --full
+  case $name in collect_prof|sq_p3|ddp2|bench) set -- "$@" --full;; esac
   local t0=$(date +%s)
   timeout -k 10 "$t" "$@" > "gpurun_out/${TAG}_$name.log" 2>&1
   local rc=$?

@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 TAG=${TAG:-pmc}
-BARGS=${BENCH_ARGS:-}
+BARGS="--full ${BENCH_ARGS:-}"
 i=0
 while IFS= read -r counters; do
   [ -z "$counters" ] && continue

@@ -18,6 +18,7 @@ SARGS="--steps 20 --warmup 5 --cpu-seconds 0 --episode-window 0 --single-step-ch
 step() {
   local name=$1 t=$2; shift 2
   [[ ",$PASSES," == *",$name,"* ]] || return 0
+  set -- "$@" --full   # every pass ends in bench.py arguments; the event re-run and the legs need --full
   timeout -k 10 "$t" "$@" > "gpurun_out/${TAG}_$name.log" 2>&1
   local rc=$?
   echo "[$name] rc=$rc"; grep -h '"metric"' "gpurun_out/${TAG}_$name.log" | cut -c1-200
