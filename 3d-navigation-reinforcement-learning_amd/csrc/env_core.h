@@ -110,8 +110,8 @@ struct Params {
     const int64_t *seeds;    // reset-only launches
     const uint8_t *mask;
     uint32_t ablate;         // unused (ablations are the compile-time VN_ABLATE)
-    int prio;                // step kernel: issue priority (bits, VOXNAV_ENV_PRIO; default 67)
-    int dflush;              // step kernel: a step's obs flush after the next step's load issue (VOXNAV_ENV_DFLUSH)
+    int prio;                // step kernel: issue priority (bits, VnTuning::prio; default 67)
+    int dflush;              // step kernel: a step's obs flush after the next step's load issue (VnTuning::dflush)
     // simpleEnv variant
     int variant, obs_dim, pd;
     uint32_t *goal;          // per agent gx | gy<<8 | gz<<16
@@ -124,7 +124,7 @@ struct Params {
     float *scratch;          // 4 KiB: targets of inactive lanes' output stores
     uint32_t *stood;         // plane-set mode PCM 2: per agent 32 words, stood-column rows (bit x of row y)
     uint2 *pnz;              // ... and per agent the plane sets whose HBM copy may be nonzero (x: rows y', y: cols x')
-    int wrec_k;              // step launches of at most wrec_k steps write the window record (VOXNAV_ENV_WREC);
+    int wrec_k;              // step launches of at most wrec_k steps write the window record (VnTuning::wrec_k);
                              // the records follow the hot state in its allocation (wrec_base)
 };
 

@@ -5,6 +5,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
 #include <string>
@@ -44,6 +45,12 @@ inline int fail(int code, const char *fmt, ...) {
     g_last_error = buf;
     return code;
 }
+
+// Process options (include/voxnav.h VN_OPT_*, vn_set_option): one definition,
+// beside vn_set_option in voxnav_env.hip; launch paths read them per call.
+constexpr int N_OPTIONS = 4;
+extern std::atomic<int32_t> g_options[N_OPTIONS];
+inline int32_t option(int opt) { return g_options[opt].load(std::memory_order_relaxed); }
 
 // Philox4x32-10 (same rounds as the env's random policy), word 0: the
 // collector's Categorical draws.  The sampler's counter is (global agent id,

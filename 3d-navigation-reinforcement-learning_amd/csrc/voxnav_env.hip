@@ -536,7 +536,7 @@ __device__ __forceinline__ void tile_flush(const Params &p, int8_t *map, const u
     }
 }
 
-// Window record (VOXNAV_ENV_WREC): a launch of at most p.wrec_k steps ends by
+// Window record (VnTuning::wrec_k): a launch of at most p.wrec_k steps ends by
 // storing the agent's 16 tile columns contiguously (16 x PH bytes, in tile
 // slot order) and sets HOT_WREC in the hot state; the next launch then fills
 // its tile from that record -- 2 (PH 8) / 4 (PH 16) 16-B loads per lane, whole
@@ -1299,10 +1299,10 @@ constexpr uint32_t kMoveDir = (2u << 0) | (0u << 2) | (3u << 4) | (1u << 6)     
 #define VN_STAGE_OBS 1
 #endif
 #ifndef VN_WREC_K_DEFAULT
-#define VN_WREC_K_DEFAULT 1  // VOXNAV_ENV_WREC when unset: launches of at most this many steps write the window record
+#define VN_WREC_K_DEFAULT 1  // VnTuning::wrec_k default: launches of at most this many steps write the window record
 #endif
 #ifndef VN_DFLUSH_DEFAULT
-#define VN_DFLUSH_DEFAULT 1  // VOXNAV_ENV_DFLUSH when unset: bit 0 byte-mark kernels, bit 1 plane-set kernels
+#define VN_DFLUSH_DEFAULT 1  // VnTuning::dflush default: bit 0 byte-mark kernels, bit 1 plane-set kernels
 #endif
 // s_setprio with a wave-uniform runtime level (the instruction takes an immediate)
 __device__ __forceinline__ void vn_setprio(int v) {
@@ -1593,14 +1593,14 @@ __global__ __launch_bounds__((PCM == 1 || PCM == 2) ? VN_PC_BLOCK : BLOCK,
     // profiles/r05/env_wave_times_rotating.log).  Paired A/B
     // (profiles/r05/ab_rotating_prio_paired.log): box +3.0 % (20-step) /
     // +1.5 % (128-step); the byte-mark kernels -0.5 %, so plane-set only.
-    // VOXNAV_ENV_PRIO bit 6 (default on).
+    // VnTuning::prio bit 6 (default on).
     const int drank = (int)(blockIdx.x / max(1u, gridDim.x / 4u));
     auto base_prio = [&](int kk) -> int {
         return (PC && (p.prio & 64) && p.K >= 8) ? min((drank + (kk >> 2)) & 3, 2) : 0;   // launches of >= 8 steps
     };
     int bprio = base_prio(0);
     if (bprio) vn_setprio(bprio);
-    // DFL: chosen by the host (launch_ph: VOXNAV_ENV_DFLUSH, launches of more
+    // DFL: chosen by the host (launch_ph: VnTuning::dflush, launches of more
     // than one step, every wave full); a separate instantiation, so the
     // waits of the loop see the same five flush stores on every path
     static_assert(!DFL || (!RESET_ONLY && (DM || PC)), "the deferred flush is for step launches of DM / PC kernels");
@@ -1646,7 +1646,7 @@ __global__ __launch_bounds__((PCM == 1 || PCM == 2) ? VN_PC_BLOCK : BLOCK,
 // box rooms +3.3 % at 20- and 128-step launches, +0.7 % one-step; P-set rooms
 // +0-1 %.  Also priority on the reward stores, the shift commit, the launch's
 // flush, or level 1 / 2 on the issue: no better.  Runtime switch per call:
-// VOXNAV_ENV_PRIO bit 0 (issue) / bit 1 (flush) / bit 6 (the rotating base
+// VnTuning::prio bit 0 (issue) / bit 1 (flush) / bit 6 (the rotating base
 // level below), default 67; the compile-time VN_SETPRIO / VN_SETPRIO_FLUSH
 // (diagnostics build) set the levels.
 #ifndef VN_SETPRIO
@@ -1981,6 +1981,7 @@ struct VnEnv {
     int device = 0;
     int N = 0;
     VnConfig cfg{};
+    VnTuning tuning{};   // validated (check_tuning); launches and kernel_label read the same copy
     int n_rooms = 0;
     int pw = 0, pd = 0, ph = 0, nbx = 0, nby = 0;
     uint32_t map_bytes = 0, agent_bytes = 0, xp_off = 0, yp_off = 0;
@@ -2060,13 +2061,9 @@ Params base_params(VnEnv *e) {
     p.gid_base = (uint64_t)e->cfg.agent_id_base;
     p.K = 1;
     p.ablate = e->ablate;
-    {   // read per call, so one env can A/B it (scripts/ab_same.py)
-        const char *ev = std::getenv("VOXNAV_ENV_PRIO");
-        p.prio = ev ? std::atoi(ev) : 67;   // bit 0: the step's load issue, 1: the obs flush, 6: rotating base
-        // bit 0: the deferred obs flush in the byte-mark kernels (PCM 3), bit 1: in the plane-set ones
-        const char *ed = std::getenv("VOXNAV_ENV_DFLUSH");
-        p.dflush = ed ? std::atoi(ed) : VN_DFLUSH_DEFAULT;
-    }
+    // the launch-time tuning (vn_set_tuning changes it on a live env: scripts/ab_same.py)
+    p.prio = e->tuning.prio;       // bit 0: the step's load issue, 1: the obs flush, 6: rotating base
+    p.dflush = e->tuning.dflush;   // bit 0: the deferred obs flush in the byte-mark kernels (PCM 3), bit 1: in the plane-set ones
     p.variant = e->variant;
     p.obs_dim = e->obs_dim;
     p.pd = e->pd;
@@ -2082,15 +2079,12 @@ Params base_params(VnEnv *e) {
     p.scratch = e->d_scratch;
     p.stood = e->d_stood;
     p.pnz = e->d_stood ? reinterpret_cast<uint2 *>(e->d_stood + (size_t)e->N * 32u) : nullptr;
-    {   // read per call (scripts/ab_same.py): launches of at most this many steps write the window record
-        const char *ew = std::getenv("VOXNAV_ENV_WREC");
-        p.wrec_k = ew ? std::atoi(ew) : VN_WREC_K_DEFAULT;
-    }
+    p.wrec_k = e->tuning.wrec_k;   // launches of at most this many steps write the window record
     return p;
 }
 
 // The deferred obs flush (env_kernel's DFL): step launches of more than one
-// step with every wave full, in the kernel modes VOXNAV_ENV_DFLUSH enables
+// step with every wave full, in the kernel modes VnTuning::dflush enables
 // (bit 0: byte marks, PCM 3; bit 1: plane sets, PCM 1 / 2).
 constexpr bool pcm_dfl_capable(int pcm) { return pcm == 1 || pcm == 2 || pcm == 3; }
 static bool use_dfl(int pcm, int N, int K, int dflush_bits) {
@@ -2138,13 +2132,6 @@ static int env_pcm(const VnEnv *e) {
 template <bool RESET_ONLY>
 int launch_pcm(VnEnv *e, int pcm, const Params &p, hipStream_t s);
 
-// VOXNAV_ENV_WREC_EARLY (read per call; default 1): the window record loaded
-// beside the hot state instead of after it (one dependent round trip less)
-static bool wrec_early() {
-    const char *ev = std::getenv("VOXNAV_ENV_WREC_EARLY");
-    return ev ? std::atoi(ev) != 0 : true;
-}
-
 template <bool RESET_ONLY>
 int launch_env(VnEnv *e, const Params &p, hipStream_t s) {
     if (e->variant == VN_VARIANT_SIMPLE)
@@ -2152,10 +2139,11 @@ int launch_env(VnEnv *e, const Params &p, hipStream_t s) {
     const int pcm = env_pcm(e);
     // the window records (wrec_fill): written by step launches of at most
     // wrec_k steps, loaded beside the state when the previous launch wrote them
+    // (VnTuning::wrec_early: instead of after it, one dependent round trip less)
     Params pw = p;
     if (!RESET_ONLY) {
         if (p.K <= p.wrec_k) pw.prio |= PRIO_WREC_SAVE;
-        if (e->wrec_written && wrec_early()) pw.prio |= PRIO_WREC_EARLY;
+        if (e->wrec_written && e->tuning.wrec_early) pw.prio |= PRIO_WREC_EARLY;
     }
     e->wrec_written = !RESET_ONLY && p.K <= p.wrec_k;
     return launch_pcm<RESET_ONLY>(e, pcm, pw, s);
@@ -2182,8 +2170,7 @@ std::string kernel_label(const VnEnv *e, bool reset_only, bool ext, bool fast, i
         return vn_simple::label(reset_only, ext, e->sline, e->sbits, e->cfg.local_map_length);
     const int pcm = env_pcm(e);
     const bool x = !reset_only && ext, f = !reset_only && fast;
-    const char *ed = std::getenv("VOXNAV_ENV_DFLUSH");
-    const bool dfl = !reset_only && !x && use_dfl(pcm, e->N, k_steps, ed ? std::atoi(ed) : VN_DFLUSH_DEFAULT);
+    const bool dfl = !reset_only && !x && use_dfl(pcm, e->N, k_steps, e->tuning.dflush);
     std::snprintf(buf, sizeof(buf), "env_kernel<%d, %s, %s, %s, %d%s>", e->ph, x ? "true" : "false",
                   f ? "true" : "false", reset_only ? "true" : "false", pcm, dfl ? ", true" : "");
     return buf;
@@ -2208,7 +2195,32 @@ void free_env(VnEnv *e) {
     delete e;
 }
 
+// the defaults of every VnTuning field, here only (vn_tuning_default)
+constexpr VnTuning kTuningDefault = {/*pcache_cap*/ -1, /*defer*/ -1, /*simple_layout*/ 0, /*prio*/ 67,
+                                     /*dflush*/ VN_DFLUSH_DEFAULT, /*wrec_k*/ VN_WREC_K_DEFAULT, /*wrec_early*/ 1};
+constexpr int PRIO_USER_BITS = 1 | 2 | 64;   // what env_kernel decodes of VnTuning::prio (the host adds PRIO_WREC_*)
+
+int check_tuning(const VnTuning &t) {
+    if (t.pcache_cap < -1 || t.pcache_cap > 2)
+        return fail(VN_ERR_INVALID, "tuning.pcache_cap must be -1, 0, 1 or 2 (got %d)", t.pcache_cap);
+    if (t.defer != -1 && t.defer != 0) return fail(VN_ERR_INVALID, "tuning.defer must be -1 or 0 (got %d)", t.defer);
+    if (t.simple_layout < 0 || t.simple_layout > 2)
+        return fail(VN_ERR_INVALID, "tuning.simple_layout must be 0, 1 or 2 (got %d)", t.simple_layout);
+    if (t.prio & ~PRIO_USER_BITS)
+        return fail(VN_ERR_INVALID, "tuning.prio must be a subset of bits %d (got %d)", PRIO_USER_BITS, t.prio);
+    if (t.dflush < 0 || t.dflush > 3) return fail(VN_ERR_INVALID, "tuning.dflush must be in 0..3 (got %d)", t.dflush);
+    if (t.wrec_k < 0) return fail(VN_ERR_INVALID, "tuning.wrec_k must be >= 0 (got %d)", t.wrec_k);
+    if (t.wrec_early != 0 && t.wrec_early != 1)
+        return fail(VN_ERR_INVALID, "tuning.wrec_early must be 0 or 1 (got %d)", t.wrec_early);
+    return VN_OK;
+}
+
+// the process options by VN_OPT_* index: values 0..max, and (below) the defaults
+constexpr int32_t kOptionMax[vn_detail::N_OPTIONS] = {2, 1, 1, 1};
+
 }  // namespace
+
+std::atomic<int32_t> vn_detail::g_options[vn_detail::N_OPTIONS] = {{0}, {1}, {1}, {0}};
 
 extern "C" {
 
@@ -2216,9 +2228,52 @@ const char *vn_last_error(void) { return g_last_error.c_str(); }
 
 int vn_abi_version(void) { return VN_ABI_VERSION; }
 
+int vn_set_option(int32_t option, int32_t value) {
+    if (option < 0 || option >= vn_detail::N_OPTIONS) return fail(VN_ERR_INVALID, "unknown option %d", option);
+    if (value < 0 || value > kOptionMax[option])
+        return fail(VN_ERR_INVALID, "option %d takes 0..%d (got %d)", option, kOptionMax[option], value);
+    vn_detail::g_options[option].store(value, std::memory_order_relaxed);
+    return VN_OK;
+}
+
+int vn_get_option(int32_t option, int32_t *value) {
+    if (!value) return fail(VN_ERR_INVALID, "NULL argument");
+    if (option < 0 || option >= vn_detail::N_OPTIONS) return fail(VN_ERR_INVALID, "unknown option %d", option);
+    *value = vn_detail::option(option);
+    return VN_OK;
+}
+
+int vn_tuning_default(VnTuning *out) {
+    if (!out) return fail(VN_ERR_INVALID, "NULL argument");
+    *out = kTuningDefault;
+    return VN_OK;
+}
+
+int vn_set_tuning(VnEnv *env, const VnTuning *tuning) {
+    if (!env || !tuning) return fail(VN_ERR_INVALID, "NULL argument");
+    if (const int rc = check_tuning(*tuning)) return rc;
+    const VnTuning &cur = env->tuning;
+    if (tuning->pcache_cap != cur.pcache_cap)
+        return fail(VN_ERR_INVALID, "tuning.pcache_cap is fixed at creation (%d, got %d)", cur.pcache_cap, tuning->pcache_cap);
+    if (tuning->defer != cur.defer)
+        return fail(VN_ERR_INVALID, "tuning.defer is fixed at creation (%d, got %d)", cur.defer, tuning->defer);
+    if (tuning->simple_layout != cur.simple_layout)
+        return fail(VN_ERR_INVALID, "tuning.simple_layout is fixed at creation (%d, got %d)", cur.simple_layout,
+                    tuning->simple_layout);
+    env->tuning = *tuning;
+    return VN_OK;
+}
+
 int vn_create(const VnRoomSet *rooms, int32_t n_agents, const VnConfig *cfg, int32_t device, VnEnv **out) {
+    return vn_create_tuned(rooms, n_agents, cfg, device, nullptr, out);
+}
+
+int vn_create_tuned(const VnRoomSet *rooms, int32_t n_agents, const VnConfig *cfg, int32_t device,
+                    const VnTuning *tuning, VnEnv **out) {
     if (!rooms || !cfg || !out) return fail(VN_ERR_INVALID, "NULL argument");
     *out = nullptr;
+    const VnTuning tun = tuning ? *tuning : kTuningDefault;
+    if (const int rc = check_tuning(tun)) return rc;
     if (n_agents <= 0) return fail(VN_ERR_INVALID, "n_agents must be > 0 (got %d)", n_agents);
     if (rooms->n_rooms <= 0 || rooms->n_rooms > VN_MAX_ROOMS)
         return fail(VN_ERR_INVALID, "n_rooms must be in 1..%d (got %d)", VN_MAX_ROOMS, rooms->n_rooms);
@@ -2331,6 +2386,7 @@ int vn_create(const VnRoomSet *rooms, int32_t n_agents, const VnConfig *cfg, int
     e->device = device;
     e->N = n_agents;
     e->cfg = *cfg;
+    e->tuning = tun;
     if (e->cfg.finish_percentage == 0.0) e->cfg.finish_percentage = 0.84;
     if (e->cfg.seed_stride == 0) e->cfg.seed_stride = n_agents;
     e->n_rooms = nr;
@@ -2344,8 +2400,7 @@ int vn_create(const VnRoomSet *rooms, int32_t n_agents, const VnConfig *cfg, int
     e->nbx = (maxW + 3) / 4;
     e->nby = (maxD + 3) / 4;
     e->ph = maxH <= 8 ? 8 : maxH <= 16 ? 16 : 32;   // whole column = one 8/16/32-byte access
-    const char *dense_env = getenv("VOXNAV_SIMPLE_DENSE");   // force the dense kernel (tests)
-    const bool dense = dense_env && dense_env[0] == '1';
+    const bool dense = tun.simple_layout == 2;   // force the dense kernel (tests)
     if (e->variant == VN_VARIANT_SIMPLE && maxW <= 64 && maxD <= 64 && !dense) {
         // bit planes: SX u64 [pd][ph], SY u64 [pw][ph], SZ u32 [pw][pd], QZ u32 [pw][pd]
         e->sbits = 1;
@@ -2353,8 +2408,8 @@ int vn_create(const VnRoomSet *rooms, int32_t n_agents, const VnConfig *cfg, int
         e->pd = maxD;
         e->map_bytes = 0;
         e->nwx = e->nwy = 0;
-        const char *sl = getenv("VOXNAV_SIMPLE_LINE");   // A/B knob: 0 keeps the word layout
-        e->sline = (maxW <= 32 && maxD <= 32 && e->ph == 8 && !(sl && sl[0] == '0')) ? 1 : 0;
+        // A/B knob: simple_layout 1 keeps the word layout
+        e->sline = (maxW <= 32 && maxD <= 32 && e->ph == 8 && tun.simple_layout != 1) ? 1 : 0;
         if (e->sline) {
             // lines: SX u32 [pd][8] (bit x), SY u32 [pw][8] (bit y), QZ u32 [pw][pd]
             e->sy_off = (uint32_t)(32 * e->pd);
@@ -2384,21 +2439,21 @@ int vn_create(const VnRoomSet *rooms, int32_t n_agents, const VnConfig *cfg, int
         e->nwy = (e->pd + 63) / 64;
         // plane-set mode: 2 = u32 rows (rooms <= 32 x 32), 1 = u64 rows (<= 64 x 64), 0 = byte marks
         e->pcache = e->ph != 8 ? 0 : (e->pw <= 32 && e->pd <= 32) ? 2 : (e->nwx == 1 && e->nwy == 1) ? 1 : 0;
-        if (const char *pc = getenv("VOXNAV_PCACHE")) {   // A/B knob: 0 off, 1 at most u64 rows
-            const int v = atoi(pc);
-            if (v >= 0 && v < e->pcache) e->pcache = v;
-        }
+        // A/B knob pcache_cap: 0 off, 1 at most u64 rows
+        if (tun.pcache_cap >= 0 && tun.pcache_cap < e->pcache) e->pcache = tun.pcache_cap;
         // byte-mark mode with plane rows of <= 2 words: defer each pass's plane marks
         // to the next step (PendMarks) so the row loads hide behind a step
-        const char *df = getenv("VOXNAV_DEFER");   // A/B knob: 0 marks in the sensing pass
-        e->defer = (e->pcache == 0 && e->nwx <= 2 && e->nwy <= 2 && !(df && df[0] == '0')) ? 1 : 0;
+        // (A/B knob defer: 0 marks in the sensing pass)
+        e->defer = (e->pcache == 0 && e->nwx <= 2 && e->nwy <= 2 && tun.defer != 0) ? 1 : 0;
         const int rowb = e->pcache == 2 ? 4 : 8;                            // plane row bytes
         e->xp_off = e->map_bytes;                                           // rows (y, z): pd * ph * nwx words
         e->yp_off = e->xp_off + (uint32_t)(e->pd * e->ph * e->nwx * rowb);  // rows (x, z): pw * ph * nwy words
         e->agent_bytes = (e->yp_off + (uint32_t)(e->pw * e->ph * e->nwy * rowb) + 15u) & ~15u;
         e->plane_bytes = e->agent_bytes - e->xp_off;
-        // placement study (diagnostics): VOXNAV_AGENT_PAD extra bytes of per-agent stride
+#ifdef VN_DIAG
+        // placement study (diagnostics build): VOXNAV_AGENT_PAD extra bytes of per-agent stride
         if (const char *ap = getenv("VOXNAV_AGENT_PAD")) e->agent_bytes += ((uint32_t)atoi(ap) + 15u) & ~15u;
+#endif
     }
 
     DeviceGuard dg(device);
@@ -2456,20 +2511,24 @@ int vn_create(const VnRoomSet *rooms, int32_t n_agents, const VnConfig *cfg, int
     VN_ALLOC(e->d_hot, (size_t)n_agents * (sizeof(uint4) + (e->variant != VN_VARIANT_SIMPLE ? 16u * (size_t)e->ph : 0u)));
     VN_ALLOC(e->d_seed, (size_t)n_agents * sizeof(uint32_t));
     {
-        // The belief maps (placement study knob, diagnostics: VOXNAV_BELIEF_OFFSET
-        // bytes into the allocation).  A VMM-mapped variant (hipMemCreate /
-        // hipMemMap chunks) was measured in round 6 and removed: on that memory
-        // the kernels' results differed from the oracle (they rely on a wave's
-        // later load seeing its own earlier store of the same bytes, e.g. a blind
-        // mark read back by the next step's entering column), and it did not
-        // remove the P-set kernels' trial-to-trial swing.
-        const char *bo = getenv("VOXNAV_BELIEF_OFFSET");
-        const size_t off = bo ? (((size_t)atoll(bo)) + 255u) & ~(size_t)255u : 0;
-        e->belief_alloc_bytes = belief_bytes + off;
-        // VOXNAV_BELIEF_CONTIG=1: a physically contiguous allocation
-        // (hipDeviceMallocContiguous; placement study)
+        // The belief maps.  A VMM-mapped variant (hipMemCreate / hipMemMap
+        // chunks) was measured in round 6 and removed: on that memory the
+        // kernels' results differed from the oracle, and it did not remove the
+        // P-set kernels' trial-to-trial swing.  The cause of the
+        // mismatch is not identified: the logs show marks written by one launch
+        // not seen by the first step of the next (Weak #1).
+        size_t off = 0;
+        bool contig = false;
+#ifdef VN_DIAG
+        // placement study (diagnostics build): VOXNAV_BELIEF_OFFSET bytes into
+        // the allocation; VOXNAV_BELIEF_CONTIG=1 a physically contiguous
+        // allocation (hipDeviceMallocContiguous)
+        if (const char *bo = getenv("VOXNAV_BELIEF_OFFSET")) off = (((size_t)atoll(bo)) + 255u) & ~(size_t)255u;
         const char *bc = getenv("VOXNAV_BELIEF_CONTIG");
-        if (bc && bc[0] == '1') {
+        contig = bc && bc[0] == '1';
+#endif
+        e->belief_alloc_bytes = belief_bytes + off;
+        if (contig) {
             const hipError_t ce = hipExtMallocWithFlags(&e->belief_alloc, e->belief_alloc_bytes, hipDeviceMallocContiguous);
             if (ce != hipSuccess) {
                 free_env(e);
@@ -2650,13 +2709,15 @@ int vn_export_belief(VnEnv *env, int8_t *belief_out, void *stream) {
     return VN_OK;
 }
 
-// diagnostics (placement study): the device address of the belief maps and the per-agent stride
+#ifdef VN_DIAG
+// diagnostics build (placement study): the device address of the belief maps and the per-agent stride
 int vn_debug_belief_addr(const VnEnv *env, uint64_t *addr, uint32_t *stride) {
     if (!env || !addr || !stride) return fail(VN_ERR_INVALID, "NULL argument");
     *addr = (uint64_t)(uintptr_t)env->d_belief;
     *stride = env->agent_bytes;
     return VN_OK;
 }
+#endif
 
 #if VN_ENV_PROF || VN_ENV_WT
 // the per-wave start / end clocks and ids of the last profiled launch

@@ -628,18 +628,12 @@ void launch(const GemmArgs &g, int batch, int splits, hipStream_t s) {
     const int tiles = ((g.M + GT - 1) / GT) * ((g.N + GT - 1) / GT);
     const dim3 grid((unsigned)tiles, (unsigned)batch, (unsigned)splits);
     // the direct-load kernel takes 16-B aligned operands whose K per split is
-    // a whole number of chunks (VN_GEMM_DL=0: the register-staged kernel, A/B knob)
+    // a whole number of chunks (VN_OPT_GEMM_DL 0: the register-staged kernel, A/B knob)
     constexpr int GKD = 16;
     auto al = [](const void *p) { return ((uintptr_t)p & 15) == 0; };
-    static const bool dl_on = [] {
-        const char *e = getenv("VN_GEMM_DL");
-        return !(e && e[0] == '0');
-    }();
-    // VN_GEMM_GKD=32: 32-deep chunks where K allows (A/B knob; half the barriers, twice the LDS)
-    static const bool gk32 = [] {
-        const char *e = getenv("VN_GEMM_GKD");
-        return e && e[0] == '3';
-    }();
+    const bool dl_on = vn_detail::option(VN_OPT_GEMM_DL) != 0;
+    // VN_OPT_GEMM_K32: 32-deep chunks where K allows (A/B knob; half the barriers, twice the LDS)
+    const bool gk32 = vn_detail::option(VN_OPT_GEMM_K32) != 0;
     const bool dl = dl_on && g.K % GKD == 0 && g.kper % GKD == 0 && g.lda % 4 == 0 && g.ldb % 4 == 0 &&
                     g.sa % 4 == 0 && g.sb % 4 == 0 && al(g.a) && al(g.b) && (!AGRAD || al(g.a2)) &&
                     (!A_KM || g.M % 4 == 0) && (!B_KM || g.N % 4 == 0);

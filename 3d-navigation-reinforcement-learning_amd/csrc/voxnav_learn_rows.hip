@@ -155,7 +155,7 @@ struct RowsFwd {
     int32_t *err;
     int64_t n_env;
     int L, B, NT;
-    int prio;                // 16-unit layout: issue priority on the hand-off path (VOXNAV_ROWS_PRIO)
+    int prio;                // 16-unit layout: issue priority on the hand-off path (VN_OPT_ROWS_PRIO)
     uint32_t *diag;          // diagnostics (NULL): placement + per-step clocks
 };
 
@@ -1156,13 +1156,11 @@ int rows_supported(int D, int H) { return D == 80 && H == 256; }
 // rows); at two per CU the two blocks of a CU run their steps in phase (their
 // matrix work shares the SIMDs, an offset start decays to alignment within ~8
 // steps), so the forward keeps the 32-unit blocks there (9.4 vs 9.9 us) and the
-// backward the 16-unit ones (14.8 vs 15.4 us).  VOXNAV_ROWS_V1=1 / _V2=1 force
+// backward the 16-unit ones (14.8 vs 15.4 us).  VN_OPT_ROWS_LAYOUT 1 / 2 force
 // one layout (A/B and tests; read per call).
 bool rows_v2(int NT, bool fwd) {
-    const char *e1 = getenv("VOXNAV_ROWS_V1");
-    if (e1 && e1[0] == '1') return false;
-    const char *e2 = getenv("VOXNAV_ROWS_V2");
-    if (e2 && e2[0] == '1') return true;
+    const int32_t layout = vn_detail::option(VN_OPT_ROWS_LAYOUT);
+    if (layout) return layout == 2;
     int dev = 0, ncu = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
@@ -1173,11 +1171,8 @@ bool rows_v2(int NT, bool fwd) {
 // the 16-unit kernels raise the issue priority on the hand-off path (wait,
 // rows, products, cell, publish) and drop it for the off-path weight
 // gradients / x part: at two blocks per CU the publishing block goes first
-// (backward 15.1 -> 14.2 us per step at 512 rows).  VOXNAV_ROWS_PRIO=0: off.
-int rows_prio() {
-    const char *e = getenv("VOXNAV_ROWS_PRIO");
-    return (e && e[0] == '0') ? 0 : 1;
-}
+// (backward 15.1 -> 14.2 us per step at 512 rows).  VN_OPT_ROWS_PRIO 0: off.
+int rows_prio() { return vn_detail::option(VN_OPT_ROWS_PRIO); }
 
 uint32_t *g_rows_diag = nullptr;   // vn_lstm_rows_set_diag (diagnostics)
 

@@ -6,8 +6,8 @@ infrastructure and is never used by the product path.)
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
-import os
 import threading
 
 from . import _build
@@ -47,18 +47,35 @@ class VnInfo(C.Structure):
     ]
 
 
+class VnTuning(C.Structure):
+    """Per-env kernel-mode tuning (include/voxnav.h); the defaults come from vn_tuning_default."""
+    _fields_ = [(f, C.c_int32) for f in ("pcache_cap", "defer", "simple_layout", "prio", "dflush", "wrec_k",
+                                         "wrec_early")]
+
+
+# process options (include/voxnav.h VN_OPT_*)
+OPTIONS = {"rows_layout": 0, "rows_prio": 1, "gemm_dl": 2, "gemm_k32": 3}
+
+
 class VoxnavError(RuntimeError):
     pass
 
 
 _lock = threading.Lock()
 _lib = None
+_lib_path = None   # use_library()
 
 P = C.c_void_p
 _SIGS = {
     "vn_last_error": (C.c_char_p, []),
     "vn_abi_version": (C.c_int, []),
     "vn_create": (C.c_int, [C.POINTER(VnRoomSet), C.c_int32, C.POINTER(VnConfig), C.c_int32, C.POINTER(P)]),
+    "vn_tuning_default": (C.c_int, [C.POINTER(VnTuning)]),
+    "vn_create_tuned": (C.c_int, [C.POINTER(VnRoomSet), C.c_int32, C.POINTER(VnConfig), C.c_int32,
+                                  C.POINTER(VnTuning), C.POINTER(P)]),
+    "vn_set_tuning": (C.c_int, [P, C.POINTER(VnTuning)]),
+    "vn_set_option": (C.c_int, [C.c_int32, C.c_int32]),
+    "vn_get_option": (C.c_int, [C.c_int32, C.POINTER(C.c_int32)]),
     "vn_destroy": (C.c_int, [P]),
     "vn_get_info": (C.c_int, [P, C.POINTER(VnInfo)]),
     "vn_reset": (C.c_int, [P, P, P, P, P]),
@@ -137,11 +154,26 @@ def load_variant(path):
     return _bind(C.CDLL(str(path)), strict=False)
 
 
+def use_library(path):
+    """Run this process on another build of the library (A/B timing of the
+    diagnostics builds under _lib/variants on the learner path, whose entry
+    points take no ``lib=``).  Before the first load() only."""
+    global _lib_path
+    with _lock:
+        if _lib is not None:
+            raise VoxnavError("use_library() must be called before the library is loaded")
+        _lib_path = str(path)
+
+
 def load(build_if_missing: bool = True):
     """Load libvoxnav.so (building it with hipcc first if it is stale)."""
     global _lib
     with _lock:
         if _lib is not None:
+            return _lib
+        if _lib_path is not None:
+            import torch  # noqa: F401
+            _lib = _bind(C.CDLL(_lib_path), strict=False)
             return _lib
         if build_if_missing and _build.needs_build():
             _build.build()
@@ -150,10 +182,7 @@ def load(build_if_missing: bool = True):
         # torch first: its libamdhip64.so.7 then satisfies our NEEDED entry, so
         # the process has one HIP runtime.
         import torch  # noqa: F401
-        # VOXNAV_LIB: another build of the library in the product's place
-        # (A/B timing of diagnostics builds under _lib/variants only)
-        alt = os.environ.get("VOXNAV_LIB")
-        _lib = _bind(C.CDLL(str(alt if alt else _build.LIB)), strict=not alt)
+        _lib = _bind(C.CDLL(str(_build.LIB)))
         return _lib
 
 
@@ -161,3 +190,24 @@ def check(rc: int, what: str = "voxnav"):
     if rc != 0:
         msg = load().vn_last_error().decode(errors="replace")
         raise VoxnavError(f"{what} failed ({rc}): {msg}")
+
+
+def get_option(name: str) -> int:
+    v = C.c_int32()
+    check(load().vn_get_option(OPTIONS[name], C.byref(v)), "vn_get_option")
+    return v.value
+
+
+def set_option(name: str, value: int) -> None:
+    check(load().vn_set_option(OPTIONS[name], int(value)), "vn_set_option")
+
+
+@contextlib.contextmanager
+def option(name: str, value: int):
+    """A process option (OPTIONS) set for the ``with`` block and restored after it."""
+    prev = get_option(name)
+    set_option(name, value)
+    try:
+        yield
+    finally:
+        set_option(name, prev)

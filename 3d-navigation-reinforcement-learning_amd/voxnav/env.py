@@ -76,14 +76,17 @@ class BatchedGridEnv:
     and ``crash_penalty``.  ``num_agents`` is the batch, ``autoreset`` the
     VecEnv behaviour.  ``variant="simple"`` selects the goal-seeking
     envs/simpleEnv.py GridAgent (obs 6L+7) instead
-    of envs/CubicEnv.py.
+    of envs/CubicEnv.py.  ``tuning`` names VnTuning fields (include/voxnav.h)
+    to override for A/B timing and mode tests, e.g. ``{"pcache_cap": 0}``;
+    the launch-time ones can be changed later with ``set_tuning``.
     """
 
     def __init__(self, num_agents: int = 1, room_path=None, rooms: Optional[RoomSet] = None,
                  local_map_length: int = 4, crash_penalty: float = -2.0, width: int = 20, depth: int = 20,
                  height: int = 12, autoreset: bool = True, device: Union[int, str, torch.device, None] = None,
                  agent_id_base: int = 0, seed_stride: Optional[int] = None,
-                 finish_percentage: float = FINISH_PERCENTAGE, variant: Union[int, str] = "cubic", lib=None):
+                 finish_percentage: float = FINISH_PERCENTAGE, variant: Union[int, str] = "cubic", lib=None,
+                 tuning: Optional[dict] = None):
         if not torch.cuda.is_available():
             raise _native.VoxnavError("BatchedGridEnv needs a ROCm GPU (torch.cuda.is_available() is False)")
         self.lib = lib if lib is not None else _native.load()
@@ -110,9 +113,15 @@ class BatchedGridEnv:
                                self.variant, self.crash_penalty, float(finish_percentage), self.agent_id_base,
                                self.seed_stride)
         h = C.c_void_p()
+        self._tuning = None   # the VnTuning in force, once it is not the library's default
         with torch.cuda.device(self.device):
-            _native.check(self.lib.vn_create(C.byref(rs), self.num_agents, C.byref(cfg), self.device.index,
-                                             C.byref(h)), "vn_create")
+            if tuning is None:   # plain vn_create: what an older A/B build passed as lib= also has
+                rc = self.lib.vn_create(C.byref(rs), self.num_agents, C.byref(cfg), self.device.index, C.byref(h))
+            else:
+                self._tuning = self._tuning_with(self._default_tuning(), tuning)
+                rc = self.lib.vn_create_tuned(C.byref(rs), self.num_agents, C.byref(cfg), self.device.index,
+                                              C.byref(self._tuning), C.byref(h))
+            _native.check(rc, "vn_create")
         self._h = h
         info = _native.VnInfo()
         _native.check(self.lib.vn_get_info(self._h, C.byref(info)), "vn_get_info")
@@ -138,6 +147,30 @@ class BatchedGridEnv:
 
     def _stream(self):
         return _stream_ptr(self.device)
+
+    def _default_tuning(self) -> _native.VnTuning:
+        t = _native.VnTuning()
+        _native.check(self.lib.vn_tuning_default(C.byref(t)), "vn_tuning_default")
+        return t
+
+    @staticmethod
+    def _tuning_with(base: _native.VnTuning, fields: dict) -> _native.VnTuning:
+        names = [f for f, _ in _native.VnTuning._fields_]
+        t = _native.VnTuning.from_buffer_copy(base)
+        for k, v in fields.items():
+            if k not in names:
+                raise ValueError(f"unknown tuning field {k!r} (VnTuning has {', '.join(names)})")
+            setattr(t, k, int(v))
+        return t
+
+    def set_tuning(self, **fields):
+        """Replace launch-time VnTuning fields (prio, dflush, wrec_k,
+        wrec_early) of the live env; the library refuses a change of a
+        creation-time field and leaves the env as it was."""
+        cur = self._tuning if self._tuning is not None else self._default_tuning()
+        t = self._tuning_with(cur, fields)
+        _native.check(self.lib.vn_set_tuning(self._h, C.byref(t)), "vn_set_tuning")
+        self._tuning = t
 
     def _seeds_tensor(self, seed) -> torch.Tensor:
         N = self.num_agents

@@ -49,7 +49,7 @@ import numpy as np
 import torch
 import torch.nn.functional as Fn
 
-from . import learn_ops, lstm_seq
+from . import _native, learn_ops, lstm_seq
 from .lstm_seq import dual_lstm
 from .policy import ActorCriticPolicy, RecurrentActorCriticPolicy
 
@@ -86,6 +86,8 @@ class PPOLearner:
         # the Adam step on the library's kernel (learn_ops.adam_step, the optimizer's
         # own state tensors); VOXNAV_NATIVE_ADAM=0: torch's fused Adam
         self.native_adam = os.environ.get("VOXNAV_NATIVE_ADAM", "1") != "0"
+        # the recurrent learner's row-layout LSTM; VOXNAV_LSTM_ROWS=0: the per-sequence packed path (A/B knob)
+        self.lstm_rows = os.environ.get("VOXNAV_LSTM_ROWS", "1") != "0"
         # the row-layout LSTM keeps all its blocks resident and hands states over
         # inside the launch: with another rank's grid on the same device that
         # co-residency is not guaranteed, so such ranks take the packed path
@@ -222,14 +224,10 @@ class PPOLearner:
     def _rows_ok(self, D: int, rows: int) -> bool:
         """The row-layout LSTM kernels take (D, rows) for this policy (cached host query)."""
         cache = self.__dict__.setdefault("_rows_cache", {})
-        # the layout knobs the library reads at every launch are part of the key,
-        # so the cached answer is always the one for the layout actually launched
-        key = (D, rows, os.environ.get("VOXNAV_ROWS_V1"), os.environ.get("VOXNAV_ROWS_V2"),
-               os.environ.get("VOXNAV_LSTM_ROWS"))
+        # the layout option decides the grid the library checks, so it is part of the key
+        key = (D, rows, _native.get_option("rows_layout"))
         if key not in cache:
-            # VOXNAV_LSTM_ROWS=0: the per-sequence packed path (A/B knob)
-            cache[key] = (not self._rows_off and os.environ.get("VOXNAV_LSTM_ROWS", "1") != "0"
-                          and lstm_seq.rows_supported(self.policy, D, rows))
+            cache[key] = self.lstm_rows and not self._rows_off and lstm_seq.rows_supported(self.policy, D, rows)
         return cache[key]
 
     def _evaluate_rows(self, buf, pk: dict):

@@ -94,6 +94,57 @@ int vn_abi_version(void);
 
 /* GridAgent.__init__ for N agents on `device` (envs/CubicEnv.py:17-74). */
 int vn_create(const VnRoomSet *rooms, int32_t n_agents, const VnConfig *cfg, int32_t device, VnEnv **out);
+
+/*
+ * Kernel-mode tuning of one env (A/B timing and the parity tests of the
+ * non-default modes).  Every mode computes the same results; the defaults
+ * (vn_tuning_default) are what vn_create uses.  The library reads no
+ * environment variable: an env's mode is what its VnTuning says.  No
+ * reference counterpart.
+ */
+typedef struct VnTuning {
+    /* fixed at creation (they decide the memory layout) */
+    int32_t pcache_cap;      /* CubicEnv plane-set mode, capped: -1 no cap (2 = u32
+                                rows for rooms <= 32 x 32, 1 = u64 rows for <= 64 x
+                                64, picked by room size), 1 at most u64 rows, 0 off
+                                (byte marks)                                       */
+    int32_t defer;           /* CubicEnv byte-mark mode: -1 auto (plane rows of <= 2
+                                words defer each pass's plane marks to the next
+                                step), 0 marks in the sensing pass                 */
+    int32_t simple_layout;   /* simpleEnv belief layout: 0 auto (line layout for
+                                rooms <= 32 x 32 x 8, bit planes of u64 words for
+                                <= 64 x 64, else the dense map), 1 keeps the word
+                                layout where auto picks lines, 2 forces the dense
+                                map                                                */
+    /* changeable on a live env (vn_set_tuning; they only pick a launch) */
+    int32_t prio;            /* step kernel issue priority, bits: 1 the step's load
+                                issue, 2 the obs flush, 64 the rotating base level
+                                of launches of >= 8 steps; default 67              */
+    int32_t dflush;          /* deferred obs flush (a step's flush after the next
+                                step's load issue; launches of more than one step),
+                                bits: 1 in the byte-mark kernels, 2 in the plane-set
+                                ones; default 1                                    */
+    int32_t wrec_k;          /* step launches of at most this many steps write the
+                                window record (0: never); default 1                */
+    int32_t wrec_early;      /* 1: a window record the previous launch wrote is
+                                loaded beside the hot state instead of after it (one
+                                dependent round trip less), 0: after; default 1    */
+} VnTuning;
+
+/* The defaults, defined here only (callers start from them and override). */
+int vn_tuning_default(VnTuning *out);
+/* vn_create with a tuning (NULL = defaults).  VN_ERR_INVALID for a field out
+ * of range: pcache_cap in {-1, 0, 1, 2}, defer in {-1, 0}, simple_layout in
+ * {0, 1, 2}, prio a subset of bits 67, dflush in 0..3, wrec_k >= 0,
+ * wrec_early in {0, 1}. */
+int vn_create_tuned(const VnRoomSet *rooms, int32_t n_agents, const VnConfig *cfg, int32_t device,
+                    const VnTuning *tuning, VnEnv **out);
+/* Replace the launch-time fields of a live env (takes effect at the next
+ * launch).  VN_ERR_INVALID, with the field named in vn_last_error(), if a
+ * creation-time field differs from what the env was created with or a value
+ * is out of range; the env is then unchanged. */
+int vn_set_tuning(VnEnv *env, const VnTuning *tuning);
+
 int vn_destroy(VnEnv *env);
 int vn_get_info(const VnEnv *env, VnInfo *info);
 
@@ -168,6 +219,26 @@ int vn_export_belief(VnEnv *env, int8_t *belief_out, void *stream);
 int vn_gae(const float *rewards, const float *values, const float *episode_starts, const float *last_values,
            const float *dones, int32_t T, int32_t N, double gamma, double gae_lambda, float *advantages,
            float *returns, void *stream);
+
+/*
+ * Process options: kernel choices of the entry points that take no handle
+ * (the row-layout LSTM and the f32 GEMMs), for A/B timing and the tests of
+ * the non-default kernels.  Every choice computes the same function.  Read
+ * at each call (relaxed atomics); VN_ERR_INVALID for an unknown option or an
+ * out-of-range value.  No reference counterpart.
+ */
+enum {
+    VN_OPT_ROWS_LAYOUT = 0,  /* vn_lstm_rows_*: 0 auto (by grid size and direction),
+                                1 blocks of 32 units, 2 blocks of 16 units; default 0 */
+    VN_OPT_ROWS_PRIO = 1,    /* 16-unit row kernels raise the issue priority on the
+                                hand-off path: 0 / 1; default 1                      */
+    VN_OPT_GEMM_DL = 2,      /* vn_gemm_f32_*: the direct-load kernel where operands
+                                allow (0: always the register-staged one); default 1 */
+    VN_OPT_GEMM_K32 = 3      /* direct-load GEMM: 32-deep chunks where K allows (half
+                                the barriers, twice the LDS): 0 / 1; default 0       */
+};
+int vn_set_option(int32_t option, int32_t value);
+int vn_get_option(int32_t option, int32_t *value);
 
 /* ------------------------------------------------------------------------
  * Rollout collector (sb3_contrib RecurrentPPO.collect_rollouts, reached

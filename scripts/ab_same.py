@@ -1,13 +1,15 @@
 #!/usr/bin/env python3
-"""Paired A/B of a per-call runtime switch (an environment variable the
-library reads at every launch, e.g. VOXNAV_ENV_PRIO) on ONE env allocation:
+"""Paired A/B of a per-launch switch -- a launch-time VnTuning field
+(env.set_tuning: prio, dflush, wrec_k, wrec_early) or a process option
+(_native.OPTIONS) -- on ONE env allocation:
 per config one env; every round resets it (same seed) and times each
 setting in alternating order, so both settings run on the same memory
 (a fresh allocation alone moves the rate by 10-15 %, scripts/ab.py).
-  python scripts/ab_same.py --var VOXNAV_ENV_PRIO --values 1,0 --configs 65536:32x32x8:10:20"""
+--lib PATH runs the process on another build (_native.use_library).
+  python scripts/ab_same.py --var prio --values 67,66 --configs 65536:32x32x8:10:20"""
 import argparse
+import contextlib
 import json
-import os
 import sys
 import time
 from pathlib import Path
@@ -16,6 +18,7 @@ REPO = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(REPO / "3d-navigation-reinforcement-learning_amd"))
 import torch  # noqa: E402
 
+from voxnav import _native  # noqa: E402
 from voxnav.env import BatchedGridEnv, Rollout  # noqa: E402
 from voxnav.rooms import box_room, load_archive_set, single_room_set  # noqa: E402
 
@@ -28,7 +31,10 @@ def main():
     ap.add_argument("--steps", type=int, default=1024)
     ap.add_argument("--warmup", type=int, default=64)
     ap.add_argument("--rounds", type=int, default=9)
+    ap.add_argument("--lib", default=None, help="another build of the library for this process")
     a = ap.parse_args()
+    if a.lib:
+        _native.use_library(a.lib)
     vals = a.values.split(",")
     for c in a.configs.split(","):
         n, room, L, F = c.split(":")[:4]
@@ -41,17 +47,22 @@ def main():
         res = {v: [] for v in vals}
         for r in range(a.rounds):
             for v in (vals if r % 2 == 0 else vals[::-1]):
-                os.environ[a.var] = v
-                e.reset(seed=42)
-                for _ in range(max(1, a.warmup // F)):
-                    e.step_random(F, out=o)
-                torch.cuda.synchronize()
-                t0 = time.perf_counter()
-                k = max(1, a.steps // F)
-                for _ in range(k):
-                    e.step_random(F, out=o)
-                torch.cuda.synchronize()
-                res[v].append(n * k * F / (time.perf_counter() - t0))
+                if a.var in _native.OPTIONS:
+                    setting = _native.option(a.var, int(v))
+                else:
+                    e.set_tuning(**{a.var: int(v)})
+                    setting = contextlib.nullcontext()
+                with setting:
+                    e.reset(seed=42)
+                    for _ in range(max(1, a.warmup // F)):
+                        e.step_random(F, out=o)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    k = max(1, a.steps // F)
+                    for _ in range(k):
+                        e.step_random(F, out=o)
+                    torch.cuda.synchronize()
+                    res[v].append(n * k * F / (time.perf_counter() - t0))
         e.close()
         base = res[vals[-1]]
         for v in vals:
@@ -60,7 +71,6 @@ def main():
             print(json.dumps({"config": c, a.var: v, "Gsteps_median": round(s[len(s) // 2] / 1e9, 3),
                               "Gsteps_min": round(s[0] / 1e9, 3), "Gsteps_max": round(s[-1] / 1e9, 3),
                               f"paired_ratio_vs_{vals[-1]}_median": round(ratio[len(ratio) // 2], 4)}), flush=True)
-        os.environ.pop(a.var, None)
 
 
 if __name__ == "__main__":

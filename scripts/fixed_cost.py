@@ -2,7 +2,7 @@
 """Per-launch fixed cost of the CubicEnv rollout-buffer kernel in the
 driver's window: after a reset and W warmup steps, one launch of F steps
 (HIP events on the launch stream), for several F; fits t(F) = fixed + F * step.
-  python scripts/fixed_cost.py [--lib path] [--warmup 5]"""
+  python scripts/fixed_cost.py [--lib path] [--warmup 5] [--tuning pcache_cap=1,dflush=3]"""
 import argparse
 import json
 import sys
@@ -23,15 +23,12 @@ ap.add_argument("--N", type=int, default=65536)
 ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--F", default="1,2,5,10,20,40")
 ap.add_argument("--reps", type=int, default=5)
-ap.add_argument("--env", default="", help="KEY=VAL settings read at env creation")
+ap.add_argument("--tuning", default="", help="field=V,... VnTuning fields of the env")
 a = ap.parse_args()
-import os  # noqa: E402
-for kv in filter(None, a.env.split(",")):
-    k, v = kv.split("=", 1)
-    os.environ[k] = v
+tuning = {k: int(v) for k, v in (kv.split("=", 1) for kv in filter(None, a.tuning.split(",")))} or None
 lib = _native.load_variant(REPO / a.lib) if a.lib else _native.load()
 env = BatchedGridEnv(num_agents=a.N, rooms=single_room_set(box_room(32, 32, 8)), local_map_length=10,
-                     autoreset=True, device="cuda:0", lib=lib)
+                     autoreset=True, device="cuda:0", lib=lib, tuning=tuning)
 Fs = [int(f) for f in a.F.split(",")]
 Fm = max(Fs)
 dev = "cuda:0"

@@ -2,7 +2,9 @@
 """The learner's f32 matrix-core products at the bench minibatch (65,536
 samples; csrc/voxnav_gemm_f32.hip through its C-ABI), each timed alone with
 HIP events: microseconds and TF/s per shape.
-python scripts/gemm_bench.py [reps]"""
+python scripts/gemm_bench.py [reps] [--lib PATH] [--k32]
+--lib: another build of the library; --k32: 32-deep chunks (process option gemm_k32)."""
+import argparse
 import ctypes as C
 import sys
 from pathlib import Path
@@ -13,9 +15,17 @@ import torch  # noqa: E402
 
 from voxnav import _native, learn_ops  # noqa: E402
 
-reps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
+ap = argparse.ArgumentParser()
+ap.add_argument("reps", type=int, nargs="?", default=20)
+ap.add_argument("--lib", default=None)
+ap.add_argument("--k32", action="store_true")
+a = ap.parse_args()
+reps = a.reps
 dev = "cuda:0"
+if a.lib:
+    _native.use_library(a.lib)
 lib = _native.load()
+_native.set_option("gemm_k32", int(a.k32))
 torch.manual_seed(0)
 M = 65536
 

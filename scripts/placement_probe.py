@@ -4,15 +4,19 @@ land in device memory.
 
 Per trial a ballast tensor of a different size is allocated first (so every
 later allocation moves), then for each variant a fresh env is created with
-the variant's knobs (environment variables vn_create reads:
-VOXNAV_AGENT_PAD, VOXNAV_BELIEF_OFFSET, VOXNAV_BELIEF_CONTIG; the round-6 VMM-mapped variant
-VOXNAV_BELIEF_VMM was removed), reset to the same
+the variant's knobs (environment variables that vn_create of a diagnostics
+build reads: VOXNAV_AGENT_PAD, VOXNAV_BELIEF_OFFSET, VOXNAV_BELIEF_CONTIG),
+reset to the same
 seed `reps` times and timed over the same launch (HIP events on the launch
 stream), so every row is the same work on a different placement.  One JSON
 line per (trial, variant): median rate, the belief base address and stride.
 
-  python scripts/placement_probe.py --config 65536:32x32x8:10:20:5 --trials 8 \
-      --variants "base:,pad4k:VOXNAV_AGENT_PAD=4096"
+The knobs and the belief address export exist only in a diagnostics build
+(VN_DIAG: scripts/build_variants.py diag:), passed with --lib:
+
+  python scripts/build_variants.py diag:
+  python scripts/placement_probe.py --lib 3d-navigation-reinforcement-learning_amd/voxnav/_lib/variants/libvoxnav_diag.so \
+      --config 65536:32x32x8:10:20:5 --trials 8 --variants "base:,pad4k:VOXNAV_AGENT_PAD=4096"
 """
 import argparse
 import ctypes as C
@@ -25,6 +29,7 @@ REPO = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(REPO / "3d-navigation-reinforcement-learning_amd"))
 import torch  # noqa: E402
 
+from voxnav import _native  # noqa: E402
 from voxnav.env import BatchedGridEnv, Rollout  # noqa: E402
 from voxnav.rooms import box_room, load_archive_set, single_room_set  # noqa: E402
 
@@ -47,9 +52,17 @@ def main():
     ap.add_argument("--trials", type=int, default=8)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--variants", default="base:")
+    ap.add_argument("--lib", required=True, help="a diagnostics build of the library (VN_DIAG)")
     ap.add_argument("--ballast-mb", type=int, default=97, help="ballast grows by this many MB per trial")
     ap.add_argument("--out-realloc", type=int, default=1, help="re-allocate the obs buffer every trial")
     a = ap.parse_args()
+    lib = _native.load_variant(a.lib if a.lib.startswith("/") else REPO / a.lib)
+    if not hasattr(lib, "vn_debug_belief_addr"):
+        sys.exit(f"{a.lib} has no vn_debug_belief_addr: the placement knobs exist only in a diagnostics build "
+                 "(python scripts/build_variants.py diag:)")
+    fn = lib.vn_debug_belief_addr
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
     n, room, L, K, W = a.config.split(":")
     n, L, K, W = int(n), int(L), int(K), int(W)
     rs = load_archive_set(room) if room.startswith("P") else single_room_set(box_room(*map(int, room.split("x"))))
@@ -69,20 +82,15 @@ def main():
             saved = {k: os.environ.get(k) for k in kv}
             os.environ.update(kv)
             try:
-                e = BatchedGridEnv(num_agents=n, rooms=rs, local_map_length=L, autoreset=True, device=dev)
+                e = BatchedGridEnv(num_agents=n, rooms=rs, local_map_length=L, autoreset=True, device=dev, lib=lib)
             finally:
                 for k, v in saved.items():
                     if v is None:
                         os.environ.pop(k, None)
                     else:
                         os.environ[k] = v
-            lib = e.lib
-            fn = getattr(lib, "vn_debug_belief_addr", None)
             addr, stride = C.c_uint64(0), C.c_uint32(0)
-            if fn is not None:
-                fn.restype = C.c_int
-                fn.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]
-                fn(e._h, C.byref(addr), C.byref(stride))
+            fn(e._h, C.byref(addr), C.byref(stride))
             us = []
             stream = torch.cuda.current_stream(dev)
             for _ in range(a.reps):

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Learner throughput: one PPO-LSTM rollout (collector) then timed PPO
-minibatch updates on it.  python scripts/ppo_bench.py --agents 16384 --batch 16384"""
+minibatch updates on it.  python scripts/ppo_bench.py --agents 16384 --batch 16384
+--lib PATH: the whole process on another build of the library; --k32: the
+GEMMs' 32-deep chunks (process option gemm_k32)."""
 import argparse
 import sys
 import time
@@ -11,6 +13,7 @@ sys.path.insert(0, str(REPO / "3d-navigation-reinforcement-learning_amd"))
 sys.path.insert(0, str(REPO))
 import torch  # noqa: E402
 
+from voxnav import _native  # noqa: E402
 from voxnav.collector import RolloutCollector  # noqa: E402
 from voxnav.env import BatchedGridEnv  # noqa: E402
 from voxnav.policy import ActorCriticPolicy, RecurrentActorCriticPolicy  # noqa: E402
@@ -25,7 +28,12 @@ def main():
     ap.add_argument("--batch", default="4096,16384")
     ap.add_argument("--minibatches", type=int, default=24)
     ap.add_argument("--policy", default="lstm")
+    ap.add_argument("--lib", default=None, help="another build of the library for this process")
+    ap.add_argument("--k32", action="store_true", help="direct-load GEMMs with 32-deep chunks")
     a = ap.parse_args()
+    if a.lib:
+        _native.use_library(a.lib)
+    _native.set_option("gemm_k32", int(a.k32))
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     pol = (RecurrentActorCriticPolicy() if a.policy == "lstm" else ActorCriticPolicy()).to(dev)

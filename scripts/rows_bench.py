@@ -1,9 +1,9 @@
 #!/usr/bin/env python3
 """Times the row-layout LSTM launches (csrc/voxnav_learn_rows.hip) alone:
 forward and forward+backward at L = 128 steps for a few row counts, in the
-layout VOXNAV_ROWS_V1 / VOXNAV_ROWS_V2 select (read per call, so one process
-can A/B them).  Kernel time by HIP events on the launch stream."""
-import os
+layout the process options rows_layout / rows_prio select (read per call, so
+one process can A/B them).  Kernel time by HIP events on the launch stream."""
+import contextlib
 import sys
 from pathlib import Path
 
@@ -11,7 +11,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[1] / "3d-navigation-rein
 import torch  # noqa: E402
 from types import SimpleNamespace  # noqa: E402
 
-from voxnav import lstm_seq  # noqa: E402
+from voxnav import _native, lstm_seq  # noqa: E402
 
 
 def run(B, L=128, reps=6):
@@ -52,15 +52,14 @@ def run(B, L=128, reps=6):
 
 def main():
     rows = [int(v) for v in (sys.argv[1] if len(sys.argv) > 1 else "128,256,512").split(",")]
-    modes = [("units32", {"VOXNAV_ROWS_V1": "1"}), ("units16", {"VOXNAV_ROWS_V2": "1"}),
-             ("units16-noprio", {"VOXNAV_ROWS_V2": "1", "VOXNAV_ROWS_PRIO": "0"}), ("auto", {}),
-             ("auto-noprio", {"VOXNAV_ROWS_PRIO": "0"})]
+    modes = [("units32", {"rows_layout": 1}), ("units16", {"rows_layout": 2}),
+             ("units16-noprio", {"rows_layout": 2, "rows_prio": 0}), ("auto", {}), ("auto-noprio", {"rows_prio": 0})]
     for B in rows:
-        for name, envs in modes:
-            for k in ("VOXNAV_ROWS_V1", "VOXNAV_ROWS_V2", "VOXNAV_ROWS_PRIO"):
-                os.environ.pop(k, None)
-            os.environ.update(envs)
-            r = run(B)
+        for name, opts in modes:
+            with contextlib.ExitStack() as stack:
+                for k, v in opts.items():
+                    stack.enter_context(_native.option(k, v))
+                r = run(B)
             if r is None:
                 print(f"B={B} {name}: not supported", flush=True)
                 continue

@@ -3,7 +3,6 @@
 (vn_lstm_rows_set_diag, diagnostics): which blocks share a CU, which groups
 they belong to, and each group's step durations."""
 import ctypes as C
-import os
 import sys
 from collections import defaultdict
 from pathlib import Path
@@ -30,7 +29,6 @@ def group_of(bid, NT, mp=0):
 
 def run(B, mp, L=128):
     dev = "cuda:0"
-    os.environ["VOXNAV_ROWS_V2"] = "1"
     D, H, N = 80, 256, max(B, 64)
     NT = -(-B // 32)
     grid = 2 * 16 * NT
@@ -108,5 +106,6 @@ def run(B, mp, L=128):
 
 
 if __name__ == "__main__":
-    for B in (256, 512):
-        run(B, 0)
+    with _native.option("rows_layout", 2):
+        for B in (256, 512):
+            run(B, 0)

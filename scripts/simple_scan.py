@@ -2,7 +2,6 @@
 """Throughput scan of the simpleEnv kernels (bit-plane vs dense map) over
 agent counts: python scripts/simple_scan.py --n 65536,262144 --dense 0,1"""
 import argparse
-import os
 import sys
 import time
 from pathlib import Path
@@ -25,7 +24,6 @@ def main():
     ap.add_argument("--steps", type=int, default=512)
     ap.add_argument("--autoreset", default="1", help="comma list of 0/1")
     ap.add_argument("--lib", default=None, help="another build of the library (e.g. -DVN_SIMPLE_PROF=1)")
-    ap.add_argument("--ablate", default="0", help="ignored: ablations are compile-time VN_ABLATE builds (see scripts/ab.py)")
     a = ap.parse_args()
     lib = raw = None
     if a.lib:
@@ -36,12 +34,9 @@ def main():
     rs = (load_archive_set(a.room) if a.room.startswith("P")
           else single_room_set(box_room(*map(int, a.room.split("x")))))
     for n in map(int, a.n.split(",")):
-        for dense, abl, ar in [(d, b, r) for d in a.dense.split(",") for b in a.ablate.split(",")
-                               for r in a.autoreset.split(",")]:
-            os.environ["VOXNAV_SIMPLE_DENSE"] = dense
-            os.environ["VOXNAV_ABLATE"] = abl
+        for dense, ar in [(d, r) for d in a.dense.split(",") for r in a.autoreset.split(",")]:
             e = BatchedGridEnv(num_agents=n, rooms=rs, local_map_length=a.L, autoreset=ar == "1", device="cuda:0",
-                               variant="simple", **({"lib": lib} if lib is not None else {}))
+                               variant="simple", lib=lib, tuning={"simple_layout": 2} if dense == "1" else None)
             e.reset(seed=42)
             F = a.F
             o = Rollout(torch.empty((F, n, e.obs_dim), device="cuda:0"), torch.empty((F, n), device="cuda:0"),
@@ -70,7 +65,7 @@ def main():
                       + f" | max wave cycles/launch={prof[6]}, max wave reset cycles/launch={prof[9]},"
                       f" resets/launch={prof[8] / launches:.0f}, wave reset events/launch={prof[10] / launches:.0f}",
                       flush=True)
-            print(f"N={n} dense={dense} ablate={abl} autoreset={ar} F={F}: {el / st * 1e6:.2f} us/step  {n * st / el / 1e9:.3f} G env-steps/s",
+            print(f"N={n} dense={dense} autoreset={ar} F={F}: {el / st * 1e6:.2f} us/step  {n * st / el / 1e9:.3f} G env-steps/s",
                   flush=True)
             e.close()
             del e, o

@@ -16,13 +16,10 @@ from voxnav.env import BatchedGridEnv, Rollout  # noqa: E402
 from voxnav.rooms import box_room, load_archive_set, single_room_set  # noqa: E402
 
 
-def make(n, room, L, ablate=0):
-    import os
-    os.environ["VOXNAV_ABLATE"] = str(ablate)   # no effect: ablations are compile-time VN_ABLATE builds
+def make(n, room, L):
     rs = load_archive_set(room) if room.startswith("P") else single_room_set(box_room(*map(int, room.split("x"))))
     e = BatchedGridEnv(num_agents=n, rooms=rs, local_map_length=L, autoreset=True, device="cuda:0")
     e.reset(seed=42)
-    os.environ.pop("VOXNAV_ABLATE", None)
     return e
 
 
@@ -62,7 +59,7 @@ def main():
     envs = {}
     for n, room, L, F, ab in cfgs:
         if (n, room, L, ab) not in envs:
-            envs[(n, room, L, ab)] = make(n, room, L, ab)
+            envs[(n, room, L, ab)] = make(n, room, L)   # ab: a label only (ablations are VN_ABLATE builds)
     res = {c: [] for c in cfgs}
     for _ in range(args.rounds):
         for c in cfgs:

@@ -5,7 +5,7 @@
 # window (scripts/env_window.py).  Every step has its own time limit; a
 # fault / abort / timeout ends the script.  Parameters (environment):
 #   TAG          output prefix under gpurun_out/
-#   AB_VARIANTS  name:lib.so[:ENV=V],...      AB_CONFIGS  N:room:L:F,...
+#   AB_VARIANTS  name:lib.so[:field=V],...      AB_CONFIGS  N:room:L:F,...
 #   SAME_LIB     lib for ab_same               SAME_VAR / SAME_VALUES / SAME_CONFIGS
 #   PMC_VARIANTS name:lib.so,...               PMC_WINDOW  env_window.py args
 set -u
@@ -26,7 +26,7 @@ if [ -n "${AB_VARIANTS:-}" ]; then
     --steps "${AB_STEPS:-256}" --rounds "${AB_ROUNDS:-5}"
 fi
 if [ -n "${SAME_VAR:-}" ]; then
-  step same 900 env ${SAME_LIB:+VOXNAV_LIB=$SAME_LIB} python3 scripts/ab_same.py --var "$SAME_VAR" \
+  step same 900 python3 scripts/ab_same.py ${SAME_LIB:+--lib "$SAME_LIB"} --var "$SAME_VAR" \
     --values "${SAME_VALUES:-1,0}" --configs "${SAME_CONFIGS:-65536:32x32x8:10:20}" --rounds "${SAME_ROUNDS:-9}"
 fi
 for item in $(echo "${PMC_VARIANTS:-}" | tr ',' ' '); do

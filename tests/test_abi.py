@@ -53,6 +53,53 @@ def test_errors_cross_the_boundary_as_codes():
     assert rc == -1 and b"variant" in lib.vn_last_error()
 
 
+def test_tuning_defaults_are_the_documented_ones():
+    from voxnav import _native
+    t = _native.VnTuning()
+    assert _native.load().vn_tuning_default(ctypes.byref(t)) == 0
+    assert {f: getattr(t, f) for f, _ in t._fields_} == {
+        "pcache_cap": -1, "defer": -1, "simple_layout": 0, "prio": 67, "dflush": 1, "wrec_k": 1, "wrec_early": 1}
+    text = HEADER.read_text()
+    fields = re.findall(r"int32_t (\w+);", text[text.index("typedef struct VnTuning"):text.index("} VnTuning;")])
+    assert fields == [f for f, _ in t._fields_]          # the binding lays the struct out as the header does
+    assert _native.load().vn_tuning_default(None) == -1
+
+
+def test_process_options_round_trip_and_reject_bad_values():
+    from voxnav import _native
+    lib = _native.load()
+    defaults = {"rows_layout": 0, "rows_prio": 1, "gemm_dl": 1, "gemm_k32": 0}
+    assert {n: _native.get_option(n) for n in _native.OPTIONS} == defaults
+    text = HEADER.read_text()
+    for name, idx in _native.OPTIONS.items():            # the binding's numbers are the header's
+        assert re.search(r"VN_OPT_%s = %d\b" % (name.upper(), idx), text), name
+    for name, value in (("rows_layout", 2), ("rows_prio", 0), ("gemm_dl", 0), ("gemm_k32", 1)):
+        with _native.option(name, value):
+            assert _native.get_option(name) == value
+        assert _native.get_option(name) == defaults[name]
+    v = ctypes.c_int32(-7)
+    assert lib.vn_set_option(99, 0) == -1 and b"unknown option" in lib.vn_last_error()
+    assert lib.vn_get_option(-1, ctypes.byref(v)) == -1 and v.value == -7
+    for name, bad in (("rows_layout", 3), ("rows_prio", 2), ("gemm_dl", -1), ("gemm_k32", 32)):
+        assert lib.vn_set_option(_native.OPTIONS[name], bad) == -1
+        assert _native.get_option(name) == defaults[name]
+
+
+def test_product_library_reads_no_environment_variable():
+    from voxnav import _build
+    out = subprocess.run(["nm", "-D", "--undefined-only", str(_build.LIB)], capture_output=True, text=True, check=True)
+    assert "hipLaunchKernel" in out.stdout               # the listing is the library's imports
+    assert "getenv" not in out.stdout
+
+
+def test_use_library_only_before_the_first_load():
+    import pytest
+    from voxnav import _native
+    _native.load()
+    with pytest.raises(_native.VoxnavError, match="before"):
+        _native.use_library(_native._build.LIB)
+
+
 def test_bindings_match_header_arity():
     """Every ctypes binding (voxnav/_native.py) takes as many arguments as
     its include/voxnav.h declaration (a stale binding passes garbage)."""

@@ -416,95 +416,137 @@ def test_gridagent_facade_matches_golden(voxnav):
             si += 1
     ag.close()
 
+def _launches_match_oracle(env, src, L, N, ks, before_launch=None):
+    """reset(42), then launches of ks[i] fused random-policy steps
+    (``before_launch(i)`` first, when given): obs bytes, f64 rewards, flags
+    and every agent's exported belief map equal the oracle's."""
+    env.reset(seed=42)
+    obs, rew, te, tr = [], [], [], []
+    for i, k in enumerate(ks):
+        if before_launch is not None:
+            before_launch(i)
+        ro = env.step_random(k, policy_seed=7, reward_f64=True)
+        obs.append(ro.obs.cpu().numpy())
+        rew.append(ro.reward.cpu().numpy())
+        te.append(ro.terminated.cpu().numpy())
+        tr.append(ro.truncated.cpu().numpy())
+    orc_env = oracle_env(src, L, n_agents=N)
+    orc = orc_env.run_random(42 + np.arange(N, dtype=np.int64), policy_seed=7, K=sum(ks), seed_stride=N)
+    assert np.concatenate(obs).tobytes() == orc["obs"].tobytes()
+    np.testing.assert_array_equal(np.concatenate(rew), orc["reward"])
+    np.testing.assert_array_equal(np.concatenate(te), orc["terminated"])
+    np.testing.assert_array_equal(np.concatenate(tr), orc["truncated"])
+    b = env.belief().cpu().numpy().astype(np.int64)
+    st = env.export_state().cpu().numpy()
+    rooms = env.room_set.rooms
+    for a in range(N):
+        W, D, H = rooms[int(st[a, 13])].shape
+        np.testing.assert_array_equal(b[a, :W, :D, :H], np.minimum(orc_env.belief(a), 63), err_msg=f"agent {a}")
+
+
 MIX_CASES = [("box:32x32x8", 10, 96), ("box:8x8x4", 4, 40), ("box:16x16x8", 7, 50), ("set:P3_training", 10, 64),
              ("box:100x40x8", 10, 48)]
-# belief modes: (VOXNAV_PCACHE, VOXNAV_DEFER)
+# belief modes: tuning (pcache_cap, defer: "1" the default -1 = auto, "0" off)
 MIX_MODES = [("0", "1"), ("0", "0"), ("1", "1"), ("2", "1")]
 
 
 @pytest.mark.parametrize("pcache,defer", MIX_MODES, ids=[f"pc{a}-df{b}" for a, b in MIX_MODES])
 @pytest.mark.parametrize("src,L,N", MIX_CASES, ids=[c[0] for c in MIX_CASES])
-def test_launch_mix_belief_matches_oracle(voxnav, monkeypatch, pcache, defer, src, L, N):
+def test_launch_mix_belief_matches_oracle(voxnav, pcache, defer, src, L, N):
     """Launches of 16, 1, 5, 3 and 30 fused steps on one env in each belief
-    mode (VOXNAV_PCACHE: 0 byte marks, 1 plane sets in u64 LDS rows, 2 in u32
+    mode (pcache_cap: 0 byte marks, 1 plane sets in u64 LDS rows, 2 in u32
     rows -- marks outside the window then live only in the marked-bit planes
-    and reach a column's bytes when it enters the window; VOXNAV_DEFER 1: in
+    and reach a column's bytes when it enters the window; defer auto: in
     byte-mark mode with plane rows of <= 2 words a sensing pass's plane marks
     are applied at the start of the next step or at the launch's end):
     obs, f64 rewards, flags and every agent's exported belief map equal the
     oracle's after 120 steps with auto-resets."""
     if pcache != "0" and src.startswith(("set:", "box:100")):
         pytest.skip("plane-set modes need PH-8 rooms of <= 64 x 64")
-    monkeypatch.setenv("VOXNAV_PCACHE", pcache)
-    monkeypatch.setenv("VOXNAV_DEFER", defer)
-    env = make_env(voxnav, src, L, n=N, autoreset=True)
-    env.reset(seed=42)
-    ks = [16, 1, 5, 16, 3, 16, 16, 1, 16, 30]
-    obs, rew, te, tr = [], [], [], []
-    for k in ks:
-        ro = env.step_random(k, policy_seed=7, reward_f64=True)
-        obs.append(ro.obs.cpu().numpy())
-        rew.append(ro.reward.cpu().numpy())
-        te.append(ro.terminated.cpu().numpy())
-        tr.append(ro.truncated.cpu().numpy())
-    orc_env = oracle_env(src, L, n_agents=N)
-    orc = orc_env.run_random(42 + np.arange(N, dtype=np.int64), policy_seed=7, K=sum(ks), seed_stride=N)
-    assert np.concatenate(obs).tobytes() == orc["obs"].tobytes()
-    np.testing.assert_array_equal(np.concatenate(rew), orc["reward"])
-    np.testing.assert_array_equal(np.concatenate(te), orc["terminated"])
-    np.testing.assert_array_equal(np.concatenate(tr), orc["truncated"])
-    b = env.belief().cpu().numpy().astype(np.int64)
-    st = env.export_state().cpu().numpy()
-    rooms = env.room_set.rooms
-    for a in range(N):
-        W, D, H = rooms[int(st[a, 13])].shape
-        np.testing.assert_array_equal(b[a, :W, :D, :H], np.minimum(orc_env.belief(a), 63), err_msg=f"agent {a}")
+    env = make_env(voxnav, src, L, n=N, autoreset=True,
+                   tuning={"pcache_cap": int(pcache), "defer": -1 if defer == "1" else 0})
+    _launches_match_oracle(env, src, L, N, [16, 1, 5, 16, 3, 16, 16, 1, 16, 30])
 
 
 WREC_CASES = [("box:32x32x8", 10, 64, "2"), ("box:16x16x8", 7, 48, "0"), ("set:P3_training", 10, 64, "3"),
               ("box:100x40x8", 10, 32, "0")]
-# window record settings: (VOXNAV_ENV_WREC: launches of at most this many steps write it, VOXNAV_ENV_WREC_EARLY)
+# window record settings: tuning (wrec_k: launches of at most this many steps write it, wrec_early)
 WREC_MODES = [("1", "1"), ("8", "1"), ("8", "0"), ("0", "1")]
 
 
 @pytest.mark.parametrize("wrec,early", WREC_MODES, ids=[f"wrec{a}-early{b}" for a, b in WREC_MODES])
 @pytest.mark.parametrize("src,L,N,pcache", WREC_CASES, ids=[f"{c[0]}-pc{c[3]}" for c in WREC_CASES])
-def test_window_record_launch_mix_matches_oracle(voxnav, monkeypatch, wrec, early, src, L, N, pcache):
+def test_window_record_launch_mix_matches_oracle(voxnav, wrec, early, src, L, N, pcache):
     """The window record (csrc/voxnav_env.hip wrec_fill): a step launch of at
-    most VOXNAV_ENV_WREC steps stores the agent's 16 window columns and the
+    most wrec_k steps stores the agent's 16 window columns and the
     next launch fills its window from them (loaded beside the state with
-    VOXNAV_ENV_WREC_EARLY=1).  Runs of one-step launches (record -> record),
+    wrec_early=1).  Runs of one-step launches (record -> record),
     short launches that write it and long ones that do not (their next launch
     falls back to the map; the P3 set's small rooms end episodes inside the
     76 steps, so auto-resets run between records): obs, f64 rewards, flags
     and every agent's belief map equal the oracle's, in each belief mode
     (pcache "3": the mode the room set selects; "0" forces byte marks)."""
-    monkeypatch.setenv("VOXNAV_ENV_WREC", wrec)
-    monkeypatch.setenv("VOXNAV_ENV_WREC_EARLY", early)
+    tuning = {"wrec_k": int(wrec), "wrec_early": int(early)}
     if pcache != "3":
-        monkeypatch.setenv("VOXNAV_PCACHE", pcache)
-    env = make_env(voxnav, src, L, n=N, autoreset=True)
-    env.reset(seed=42)
-    ks = [1, 1, 1, 5, 1, 1, 16, 1, 2, 1, 1, 8, 1, 30, 1, 1]
-    obs, rew, te, tr = [], [], [], []
-    for k in ks:
-        ro = env.step_random(k, policy_seed=7, reward_f64=True)
-        obs.append(ro.obs.cpu().numpy())
-        rew.append(ro.reward.cpu().numpy())
-        te.append(ro.terminated.cpu().numpy())
-        tr.append(ro.truncated.cpu().numpy())
-    orc_env = oracle_env(src, L, n_agents=N)
-    orc = orc_env.run_random(42 + np.arange(N, dtype=np.int64), policy_seed=7, K=sum(ks), seed_stride=N)
-    assert np.concatenate(obs).tobytes() == orc["obs"].tobytes()
-    np.testing.assert_array_equal(np.concatenate(rew), orc["reward"])
-    np.testing.assert_array_equal(np.concatenate(te), orc["terminated"])
-    np.testing.assert_array_equal(np.concatenate(tr), orc["truncated"])
-    b = env.belief().cpu().numpy().astype(np.int64)
-    st = env.export_state().cpu().numpy()
-    rooms = env.room_set.rooms
-    for a in range(N):
-        W, D, H = rooms[int(st[a, 13])].shape
-        np.testing.assert_array_equal(b[a, :W, :D, :H], np.minimum(orc_env.belief(a), 63), err_msg=f"agent {a}")
+        tuning["pcache_cap"] = int(pcache)
+    env = make_env(voxnav, src, L, n=N, autoreset=True, tuning=tuning)
+    _launches_match_oracle(env, src, L, N, [1, 1, 1, 5, 1, 1, 16, 1, 2, 1, 1, 8, 1, 30, 1, 1])
+
+
+# ---- the tuning boundary (VnTuning through vn_create_tuned / vn_set_tuning) ----
+TUNE_SRC, TUNE_L, TUNE_N = "box:8x8x4", 4, 40
+# every variable the library once read, at its non-default value
+OLD_VARIABLES = {"VOXNAV_PCACHE": "0", "VOXNAV_DEFER": "0", "VOXNAV_ENV_DFLUSH": "0", "VOXNAV_ENV_WREC": "0",
+                 "VOXNAV_SIMPLE_LINE": "0", "VOXNAV_SIMPLE_DENSE": "1"}
+
+
+def _labels(voxnav, **kw):
+    out = []
+    for variant in ("cubic", "simple"):
+        env = make_env(voxnav, TUNE_SRC, TUNE_L, n=TUNE_N, variant=variant, **kw)
+        out += [env.kernel_label(1), env.kernel_label(16)]
+        env.close()
+    return out
+
+
+def test_process_environment_does_not_steer_the_library(voxnav, monkeypatch):
+    """With every former VOXNAV_* knob set to its non-default value, a fresh
+    CubicEnv and a fresh simpleEnv launch the same kernels (1- and 16-step
+    labels) as without them; the same mode asked for through the tuning does
+    change the kernel."""
+    plain = _labels(voxnav)
+    for k, v in OLD_VARIABLES.items():
+        monkeypatch.setenv(k, v)
+    assert _labels(voxnav) == plain
+    capped = _labels(voxnav, tuning={"pcache_cap": 0})
+    assert capped[1] != plain[1]            # kernel_label(16) of the CubicEnv
+
+
+def test_create_tuned_rejects_out_of_range_field(voxnav):
+    from voxnav._native import VoxnavError
+    with pytest.raises(VoxnavError, match=r"\(-1\).*pcache_cap"):      # VN_ERR_INVALID
+        make_env(voxnav, TUNE_SRC, TUNE_L, n=TUNE_N, tuning={"pcache_cap": 5})
+    with pytest.raises(ValueError, match="unknown tuning field"):
+        make_env(voxnav, TUNE_SRC, TUNE_L, n=TUNE_N, tuning={"pcache": 0})
+
+
+def test_set_tuning_refuses_creation_time_field_and_leaves_env_intact(voxnav):
+    from voxnav._native import VoxnavError
+    env = make_env(voxnav, TUNE_SRC, TUNE_L, n=TUNE_N, autoreset=True)
+    label = env.kernel_label(16)
+    with pytest.raises(VoxnavError, match=r"\(-1\).*pcache_cap"):
+        env.set_tuning(pcache_cap=0)
+    assert env.kernel_label(16) == label
+    _launches_match_oracle(env, TUNE_SRC, TUNE_L, TUNE_N, [20])
+
+
+def test_set_tuning_window_record_off_mid_run_matches_oracle(voxnav):
+    """wrec_k=0 set on a live env between one-step launches: the launch before
+    it wrote the window record, the next one still fills its window from that
+    record, and neither of the two after writes one."""
+    env = make_env(voxnav, TUNE_SRC, TUNE_L, n=TUNE_N, autoreset=True)
+    _launches_match_oracle(env, TUNE_SRC, TUNE_L, TUNE_N, [1, 1, 1],
+                           before_launch=lambda i: env.set_tuning(wrec_k=0) if i == 1 else None)
 
 
 @pytest.mark.parametrize("src", ["box:32x32x8", "box:16x16x8"])

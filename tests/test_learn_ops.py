@@ -149,7 +149,7 @@ def _rows_reference(x, env, start, keep, hs, cs, lstm, l):
 @pytest.mark.parametrize("L,B,N,p_start", [(24, 512, 600, 0.03), (9, 37, 40, 0.2), (128, 64, 64, 0.01),
                                            (128, 512, 512, 0.004), (1, 1, 4, 0.5), (2, 33, 8, 0.5),
                                            (5, 289, 300, 1.0)])
-def test_dual_lstm_rows_matches_float64(L, B, N, p_start, layout, monkeypatch):
+def test_dual_lstm_rows_matches_float64(L, B, N, p_start, layout):
     """The persistent row-layout LSTM (csrc/voxnav_learn_rows.hip: weights
     resident, in-launch h / partial-dh hand-offs between the unit blocks of a
     row tile) against a float64 restatement: outputs and the weight / bias
@@ -160,17 +160,17 @@ def test_dual_lstm_rows_matches_float64(L, B, N, p_start, layout, monkeypatch):
     edge shapes: one step of one row, two steps of a 33-row batch (one full
     tile and a 1-row tile), and a batch where every row starts a sequence at
     every step (no state crosses a step: only the stored states).
-    Both layouts, forced: 16 unit blocks of 16 units (VOXNAV_ROWS_V2=1; two
-    blocks per CU at 512 rows) and 8 of 32 (VOXNAV_ROWS_V1=1), and the
+    Both layouts, forced: 16 unit blocks of 16 units (option rows_layout 2; two
+    blocks per CU at 512 rows) and 8 of 32 (rows_layout 1), and the
     default pick per direction."""
+    from voxnav import _native
+    with _native.option("rows_layout", {"auto": 0, "units32": 1, "units16": 2}[layout]):
+        _dual_lstm_rows_vs_float64(L, B, N, p_start)
+
+
+def _dual_lstm_rows_vs_float64(L, B, N, p_start):
     from types import SimpleNamespace
     from voxnav import lstm_seq
-    monkeypatch.delenv("VOXNAV_ROWS_V1", raising=False)
-    monkeypatch.delenv("VOXNAV_ROWS_V2", raising=False)
-    if layout == "units32":
-        monkeypatch.setenv("VOXNAV_ROWS_V1", "1")
-    elif layout == "units16":
-        monkeypatch.setenv("VOXNAV_ROWS_V2", "1")
     dev = "cuda:0"
     D, H = 80, 256
     torch.manual_seed(L * B + N)

@@ -93,19 +93,20 @@ def test_simple_random_rollout_matches_oracle(voxnav, src, L, N, K):
 # the word-layout pipelined kernel (simple_pipe_kernel: the default for rooms
 # higher than 8 or wider / deeper than 32) on rooms the line layout takes by default
 PIPE_CASES = [("box:8x8x4", 4, 300, 200), ("set:P2_training", 4, 1024, 250), ("ctor:12x10x6", 10, 256, 200)]
+WORD_LAYOUT = {"simple_layout": 1}
+DENSE_LAYOUT = {"simple_layout": 2}
 
 
 @pytest.mark.parametrize("src,L,N,K", PIPE_CASES, ids=[f"{c[0]}-L{c[1]}" for c in PIPE_CASES])
-def test_simple_word_layout_kernel_matches_oracle(voxnav, monkeypatch, src, L, N, K):
-    monkeypatch.setenv("VOXNAV_SIMPLE_LINE", "0")
-    env = make_env(src, L, n=8)
+def test_simple_word_layout_kernel_matches_oracle(voxnav, src, L, N, K):
+    env = make_env(src, L, n=8, tuning=WORD_LAYOUT)
     assert env.kernel_label(16).startswith("simple_pipe_kernel<")
     env.close()
-    _rollout_vs_oracle(src, L, N, K)
+    _rollout_vs_oracle(src, L, N, K, tuning=WORD_LAYOUT)
 
 
 # the dense int8 map kernel: rooms wider or deeper than 64 cells, or forced
-# with VOXNAV_SIMPLE_DENSE=1 (the bit-plane kernel covers the cases above)
+# with tuning simple_layout=2 (the bit-plane kernel covers the cases above)
 DENSE_CASES = [
     ("ctor:70x9x5", 4, 256, 200, False),
     ("ctor:10x66x5", 6, 128, 150, False),
@@ -115,14 +116,12 @@ DENSE_CASES = [
 
 
 @pytest.mark.parametrize("src,L,N,K,force", DENSE_CASES, ids=[f"{c[0]}-L{c[1]}" for c in DENSE_CASES])
-def test_simple_dense_layout_matches_oracle(voxnav, monkeypatch, src, L, N, K, force):
-    if force:
-        monkeypatch.setenv("VOXNAV_SIMPLE_DENSE", "1")
-    _rollout_vs_oracle(src, L, N, K)
+def test_simple_dense_layout_matches_oracle(voxnav, src, L, N, K, force):
+    _rollout_vs_oracle(src, L, N, K, tuning=DENSE_LAYOUT if force else None)
 
 
-def _rollout_vs_oracle(src, L, N, K):
-    env = make_env(src, L, n=N, autoreset=True)
+def _rollout_vs_oracle(src, L, N, K, tuning=None):
+    env = make_env(src, L, n=N, autoreset=True, tuning=tuning)
     seeds = 42 + np.arange(N, dtype=np.int64)
     obs0 = env.reset(seed=42).cpu().numpy()
     oenv = oracle_env(src, L, n_agents=N, variant=1)
@@ -150,13 +149,13 @@ def _rollout_vs_oracle(src, L, N, K):
 
 
 def _bench_shaped_run(N, sample, K, F=128, src="box:32x32x8", L=4, policy_seed=42,
-                      label="simple_line_kernel<4, false>"):
+                      label="simple_line_kernel<4, false>", tuning=None):
     """The bench's simpleEnv call: ``step_random(out=...)`` in F-step launches
     into a reused [F, N, 6L+7] chunk, f32 reward, no action record; the
     sampled agents compared with the oracle launch by launch (the per-agent
     reset draw-ahead is carried across launches)."""
     from voxnav.env import Rollout
-    env = make_env(src, L, n=N, autoreset=True)
+    env = make_env(src, L, n=N, autoreset=True, tuning=tuning)
     assert env.kernel_label(F) == label
     dev = env.device
     D = env.obs_dim
@@ -220,13 +219,13 @@ def test_simple_bench_instantiation_full_batch_sampled(voxnav):
     assert ends["terminated"] > 0
 
 
-def test_simple_word_layout_bench_shape_sampled(voxnav, monkeypatch):
-    """The word-layout kernel (VOXNAV_SIMPLE_LINE=0) in the bench's launches:
+def test_simple_word_layout_bench_shape_sampled(voxnav):
+    """The word-layout kernel (tuning simple_layout=1) in the bench's launches:
     4,096 agents, one sampled per 64-agent block, 1,280 steps."""
-    monkeypatch.setenv("VOXNAV_SIMPLE_LINE", "0")
     N = 4096
     blocks = np.arange(N // 64, dtype=np.int64)
-    _bench_shaped_run(N, blocks * 64 + (blocks * 23 + 5) % 64, 1280, label="simple_pipe_kernel<4, false>")
+    _bench_shaped_run(N, blocks * 64 + (blocks * 23 + 5) % 64, 1280, label="simple_pipe_kernel<4, false>",
+                      tuning=WORD_LAYOUT)
 
 
 def test_simple_step_actions_terminal_obs(voxnav):
