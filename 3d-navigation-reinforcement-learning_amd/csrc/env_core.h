@@ -1,10 +1,12 @@
 // env_core.h -- device code shared by the CubicEnv (voxnav_env.hip) and
 // simpleEnv (voxnav_simple.hip) translation units: the packed agent / room
-// records, the launch parameters, CPython's MT19937 seeding restated for the
-// device, the Philox policy and the obs-store helpers.  Everything is in an
-// anonymous namespace: each translation unit gets its own copy (including
-// the __constant__ MT table, which each unit fills through its own
-// ensure_mt_table).
+// records, CPython's MT19937 seeding restated for the device, the Philox
+// policy and the obs-store helpers.  Everything is in an anonymous namespace:
+// each translation unit gets its own copy (including the __constant__ MT
+// table, which each unit fills through its own ensure_mt_table).  The launch
+// parameters and the two units' host interfaces (vn_cubic, vn_simple) are in
+// env_params.h, the constants shared with the host tables in env_plan.h; the
+// host side of the boundary (voxnav_api.hip) includes those two only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -19,6 +21,8 @@
 #include <vector>
 
 #include "vn_common.h"
+#include "env_params.h"
+#include "env_plan.h"
 
 // Diagnostics only: VN_ABLATE bits skip parts of the step (results invalid)
 // in a separately built library (scripts/ab.py); 0 in the product.  A
@@ -66,66 +70,6 @@ struct Agent {
     bool done, last_bump, near_wall, was_near_wall;
     uint32_t step_count, visited, bumps, move_mask;
     int cid, room;
-};
-
-// Env-constant values the (rare, out-of-line) reset path reads from device
-// memory, so they need not stay live in SGPRs across the step loop.
-struct EnvConst {
-    const uint4 *rooms;
-    const uint2 *rays;
-    const uint32_t *starts;
-    int32_t *err;
-    int n_rooms, use_room_draw, nby, pcache;
-    uint32_t agent_bytes, xp_off, map_bytes, plane_bytes;   // plane_bytes: the planes a reset clears
-    const uint4 *wimg;       // plane-set mode: per room, the bricked map with latent wall bits
-};
-
-struct Params {
-    const EnvConst *envc;
-    uint4 *hot;
-    uint32_t *next_seed;
-    int8_t *belief;
-    const uint4 *rooms;
-    const uint2 *rays;
-    const uint32_t *starts;
-    const float *lut;
-    int32_t *err;
-    int N, L, nby, ph;
-    uint32_t map_bytes;      // byte map (bricked) per agent
-    uint32_t agent_bytes;    // stride: byte map + x-plane + y-plane
-    uint32_t xp_off, yp_off; // plane offsets inside the agent block
-    int nwx, nwy;            // u64 words per plane row
-    int n_rooms, use_room_draw, autoreset;
-    uint32_t seed_stride;
-    double crash_penalty, finish;
-    uint64_t gid_base;
-    // per call
-    int K;
-    const int32_t *actions;  // NULL -> Philox random policy
-    uint64_t policy_seed, t0;
-    int32_t *actions_out;
-    float *obs, *reward, *terminal_obs;
-    double *reward64;
-    uint8_t *term, *trunc;
-    const int64_t *seeds;    // reset-only launches
-    const uint8_t *mask;
-    uint32_t ablate;         // unused (ablations are the compile-time VN_ABLATE)
-    int prio;                // step kernel: issue priority (bits, VnTuning::prio; default 67)
-    int dflush;              // step kernel: a step's obs flush after the next step's load issue (VnTuning::dflush)
-    // simpleEnv variant
-    int variant, obs_dim, pd;
-    uint32_t *goal;          // per agent gx | gy<<8 | gz<<16
-    uint4 *predraw;          // simpleEnv: per agent a reset draw computed ahead {start|room<<24, goal, seed, valid}
-    int sbits;               // simpleEnv bit-plane layout (rooms up to 64 x 64 x 31)
-    uint32_t sy_off, sz_off, qz_off;
-    int sline;               // simpleEnv line layout (rooms up to 32 x 32 x 8; simple_line_kernel)
-    const int8_t *wimg;      // plane-set mode (CubicEnv, PH 8, rooms <= 64 x 64): latent-wall room images
-    int pcache;
-    float *scratch;          // 4 KiB: targets of inactive lanes' output stores
-    uint32_t *stood;         // plane-set mode PCM 2: per agent 32 words, stood-column rows (bit x of row y)
-    uint2 *pnz;              // ... and per agent the plane sets whose HBM copy may be nonzero (x: rows y', y: cols x')
-    int wrec_k;              // step launches of at most wrec_k steps write the window record (VnTuning::wrec_k);
-                             // the records follow the hot state in its allocation (wrec_base)
 };
 
 __device__ __forceinline__ Agent unpack(uint4 s) {
@@ -432,14 +376,6 @@ __device__ __forceinline__ uint4 philox4x32_10(uint64_t key, uint64_t gid, uint6
 // ----------------------------------------------------------------------------
 constexpr int GROUP = 4;
 constexpr uint32_t KNOWN = 0x80u, WALLB = 0xC0u;
-// LDS table: [0,256) obs value of each belief byte; [256,262) f32(a/5);
-// [264,281) f32(c/L)   (get_obs :273-275, :284, :287)
-constexpr int TAB_ACTION = 256, TAB_CID = 264, TAB_SIZE = 288;
-// after the CubicEnv table in the same device buffer: the simpleEnv reward of
-// each event code (bit 0 bump, 1 repeated move, 2 goal, 3 explored), 16 f32
-// then 16 f64, each the reference's f64 sum in its order (envs/simpleEnv.py:189-217)
-constexpr int TAB_SREW = TAB_SIZE, TAB_SREW64 = TAB_SIZE + 16, TAB_ALL = TAB_SIZE + 48;
-
 __device__ __forceinline__ int decode_count(uint32_t b) {   // center cell: known free or unknown
     return (b & KNOWN) ? (int)(b & 0x3fu) : -1;
 }
@@ -524,11 +460,3 @@ int ensure_mt_table(int device) {
 }
 
 }  // namespace
-
-// the simpleEnv unit (voxnav_simple.hip), called by voxnav_env.hip's host side
-namespace vn_simple {
-int ensure_mt(int device);
-int launch(bool reset_only, int sline, int sbits, int L, int N, int obs_dim, const void *params, hipStream_t s);
-std::string label(bool reset_only, bool ext, int sline, int sbits, int L);
-int export_belief(const void *params, int8_t *out, int pw, int pd, hipStream_t s);
-}  // namespace vn_simple

@@ -1,6 +1,6 @@
-// vn_common.h -- helpers shared by the libvoxnav translation units
-// (error reporting across the C-ABI: negative VN_ERR_* codes plus a
-// thread-local message returned by vn_last_error()).
+// vn_common.h -- helpers shared by the libvoxnav translation units: the
+// error reporting of vn_error.h, the compile-time knob guard, the process
+// options and the collector's Philox word.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <string>
 
+#include "vn_error.h"
 #include "voxnav.h"
 
 // Compile-time knobs -- the ablations (VN_ABLATE), timing diagnostics
@@ -34,20 +35,8 @@
 
 namespace vn_detail {
 
-inline thread_local std::string g_last_error;
-
-inline int fail(int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_last_error = buf;
-    return code;
-}
-
 // Process options (include/voxnav.h VN_OPT_*, vn_set_option): one definition,
-// beside vn_set_option in voxnav_env.hip; launch paths read them per call.
+// beside vn_set_option in voxnav_api.hip; launch paths read them per call.
 constexpr int N_OPTIONS = 4;
 extern std::atomic<int32_t> g_options[N_OPTIONS];
 inline int32_t option(int opt) { return g_options[opt].load(std::memory_order_relaxed); }

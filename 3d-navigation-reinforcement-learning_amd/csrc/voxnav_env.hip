@@ -29,6 +29,12 @@
 // reference's operation order (file compiled with -ffp-contract=off), obs
 // window values from a 23-entry f32 table built on the host with IEEE f32
 // division, obs[68], [71], [72] as f64 quotients rounded to f32.
+//
+// This file is the CubicEnv kernel unit: the device code, gae_kernel, and at
+// the end the vn_cubic interface (env_params.h) -- which env_kernel
+// instantiation a call launches, its label, and the state / belief exports.
+// The C-ABI entry points, VnEnv and the host-side planning (room tables,
+// per-agent layout, LUT) are in voxnav_api.hip and env_plan.h.
 
 #include "env_core.h"
 
@@ -156,21 +162,7 @@ __device__ __forceinline__ bool col_differs(const Col<PH> &a, const Col<PH> &b) 
     return d;
 }
 
-// Column index of (x, y) in the bricked map: bricks of 4 x 4 columns, x-major;
-// inside a brick y fast ((x & 3) << 2 | (y & 3)), or x fast with VN_BRICK_T 1
-// (diagnostics: a lane's 4 window columns -- one y, 4 consecutive x -- are
-// then contiguous in the brick row), or 2 x 2 sub-bricks with VN_BRICK_T 2
-// (a PH-16 64-B piece holds a 2 x 2 block of columns).
-#ifndef VN_BRICK_T
-#define VN_BRICK_T 0
-#endif
-__host__ __device__ __forceinline__ uint32_t bcol(int x, int y, int nby) {
-    const uint32_t in = VN_BRICK_T == 2 ? (uint32_t)(((x & 2) << 2) | ((y & 2) << 1) | ((x & 1) << 1) | (y & 1))
-                        : VN_BRICK_T ? (uint32_t)(((y & 3) << 2) | (x & 3))
-                                     : (uint32_t)(((x & 3) << 2) | (y & 3));
-    return ((uint32_t)((x >> 2) * nby + (y >> 2)) << 4) + in;
-}
-
+// byte (x, y, z) of the bricked map (bcol: env_plan.h)
 template <int PH>
 __device__ __forceinline__ uint32_t boff(int x, int y, int z, int nby) {
     return bcol(x, y, nby) * (uint32_t)PH + (uint32_t)z;
@@ -202,8 +194,7 @@ constexpr int STAGE_WORDS_F = 16 * VN_OBS_DIM;
 // values that never occur (bit7 clear but not 0x00 / 0x40; 0xC1..0xFF), whose
 // LUT entries are the tail's values: 0.0, 1.0, f32(a/5), f32(c/L).  obs[72]
 // (a quotient with many values) gets a code per agent of the block whose LUT
-// entry the agent rewrites each step (tc_slot).
-constexpr uint32_t TC_ZERO = 0x01u, TC_ONE = 0x02u, TC_ACT = 0x08u, TC_CID = 0x10u;
+// entry the agent rewrites each step (tc_slot).  TC_*: env_plan.h, with the LUT.
 constexpr uint32_t TC_ZERO4 = TC_ZERO * 0x01010101u;
 __device__ __forceinline__ uint32_t tc_slot(int agent_in_block) {        // 64 codes: 0x41..0x60, 0xC1..0xE0
     return agent_in_block < 32 ? 0x41u + (uint32_t)agent_in_block : 0xC1u + (uint32_t)(agent_in_block - 32);
@@ -426,10 +417,7 @@ __device__ __forceinline__ int tslot(int x, int y) { return ((x & 3) << 2) | (y 
 // Plane-set mode: the latent-wall room images, VN_WIMG_REP copies per room
 // ([room][copy][map_bytes]); agent a reads copy a % VN_WIMG_REP, so the
 // launch's window fill (every agent reading its room's image at once) is
-// spread over more L2 lines (diagnostics knob, default one copy).
-#ifndef VN_WIMG_REP
-#define VN_WIMG_REP 1
-#endif
+// spread over more L2 lines (diagnostics knob, default one copy: env_plan.h).
 __device__ __forceinline__ const int8_t *room_image(const int8_t *wimg, int room, uint32_t map_bytes) {
     const uint32_t agent = (blockIdx.x * blockDim.x + threadIdx.x) >> 2;
     return wimg + ((size_t)room * VN_WIMG_REP + (VN_WIMG_REP > 1 ? agent % VN_WIMG_REP : 0u)) * map_bytes;
@@ -1298,12 +1286,6 @@ constexpr uint32_t kMoveDir = (2u << 0) | (0u << 2) | (3u << 4) | (1u << 6)     
 #ifndef VN_STAGE_OBS
 #define VN_STAGE_OBS 1
 #endif
-#ifndef VN_WREC_K_DEFAULT
-#define VN_WREC_K_DEFAULT 1  // VnTuning::wrec_k default: launches of at most this many steps write the window record
-#endif
-#ifndef VN_DFLUSH_DEFAULT
-#define VN_DFLUSH_DEFAULT 1  // VnTuning::dflush default: bit 0 byte-mark kernels, bit 1 plane-set kernels
-#endif
 // s_setprio with a wave-uniform runtime level (the instruction takes an immediate)
 __device__ __forceinline__ void vn_setprio(int v) {
     if (v <= 0) __builtin_amdgcn_s_setprio(0);
@@ -1972,116 +1954,9 @@ __global__ __launch_bounds__(256) void gae_kernel(const float *__restrict__ rew,
     }
 }
 
-}  // namespace
-
 // ============================================================================
-// host side
+// host side: which kernel a CubicEnv call launches (vn_cubic, env_params.h)
 // ============================================================================
-struct VnEnv {
-    int device = 0;
-    int N = 0;
-    VnConfig cfg{};
-    VnTuning tuning{};   // validated (check_tuning); launches and kernel_label read the same copy
-    int n_rooms = 0;
-    int pw = 0, pd = 0, ph = 0, nbx = 0, nby = 0;
-    uint32_t map_bytes = 0, agent_bytes = 0, xp_off = 0, yp_off = 0;
-    uint32_t plane_bytes = 0;   // CubicEnv: the marked-bit planes after the map (what a reset clears)
-    int nwx = 1, nwy = 1;
-    size_t device_bytes = 0;
-    std::vector<uint32_t> total_free;
-    uint4 *d_rooms = nullptr;
-    uint2 *d_rays = nullptr;
-    uint32_t *d_starts = nullptr;
-    float *d_lut = nullptr;
-    uint4 *d_hot = nullptr;
-    uint32_t *d_seed = nullptr;
-    int8_t *d_belief = nullptr;
-    int32_t *d_err = nullptr;
-    EnvConst *d_envc = nullptr;
-    uint32_t *d_goal = nullptr;
-    uint4 *d_predraw = nullptr;
-    uint32_t ablate = 0;
-    int variant = 0, obs_dim = VN_OBS_DIM;
-    int sbits = 0;     // simpleEnv bit-plane layouts (rooms <= 64 x 64 x 31), else the dense map
-    uint32_t sy_off = 0, sz_off = 0, qz_off = 0;
-    int sline = 0;     // simpleEnv line layout (simple_line_kernel), rooms <= 32 x 32 x 8
-    int defer = 0;     // CubicEnv byte-mark mode with deferred plane marks (PCM 3; rows <= 2 words)
-    int pcache = 0;    // CubicEnv plane-set mode (PH 8, rooms <= 64 x 64): see pset_fill
-    int8_t *d_wimg = nullptr;
-    float *d_scratch = nullptr;   // 8 KiB: targets of dummy output stores (the deferred flush's first step)
-    uint32_t *d_stood = nullptr;  // PCM 2: per agent 32 stood rows, then per agent the nonzero-set masks (uint2)
-    bool wrec_written = false;    // the last step launch wrote every agent's window record (wrec_fill)
-    // the belief allocation (d_belief may sit at an offset inside it: placement study knobs, vn_create)
-    void *belief_alloc = nullptr;
-    size_t belief_alloc_bytes = 0;
-};
-
-namespace {
-
-struct DeviceGuard {
-    int prev = -1;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) (void)hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
-Params base_params(VnEnv *e) {
-    Params p;
-    std::memset(&p, 0, sizeof(p));
-    p.envc = e->d_envc;
-    p.hot = e->d_hot;
-    p.next_seed = e->d_seed;
-    p.belief = e->d_belief;
-    p.rooms = e->d_rooms;
-    p.rays = e->d_rays;
-    p.starts = e->d_starts;
-    p.lut = e->d_lut;
-    p.err = e->d_err;
-    p.N = e->N;
-    p.L = e->cfg.local_map_length;
-    p.nby = e->nby;
-    p.ph = e->ph;
-    p.map_bytes = e->map_bytes;
-    p.agent_bytes = e->agent_bytes;
-    p.xp_off = e->xp_off;
-    p.yp_off = e->yp_off;
-    p.nwx = e->nwx;
-    p.nwy = e->nwy;
-    p.n_rooms = e->n_rooms;
-    p.use_room_draw = e->cfg.use_room_draw;
-    p.autoreset = e->cfg.autoreset;
-    p.seed_stride = (uint32_t)(uint64_t)e->cfg.seed_stride;
-    p.crash_penalty = e->cfg.crash_penalty;
-    p.finish = e->cfg.finish_percentage;
-    p.gid_base = (uint64_t)e->cfg.agent_id_base;
-    p.K = 1;
-    p.ablate = e->ablate;
-    // the launch-time tuning (vn_set_tuning changes it on a live env: scripts/ab_same.py)
-    p.prio = e->tuning.prio;       // bit 0: the step's load issue, 1: the obs flush, 6: rotating base
-    p.dflush = e->tuning.dflush;   // bit 0: the deferred obs flush in the byte-mark kernels (PCM 3), bit 1: in the plane-set ones
-    p.variant = e->variant;
-    p.obs_dim = e->obs_dim;
-    p.pd = e->pd;
-    p.goal = e->d_goal;
-    p.predraw = e->d_predraw;
-    p.sbits = e->sbits;
-    p.sy_off = e->sy_off;
-    p.sz_off = e->sz_off;
-    p.qz_off = e->qz_off;
-    p.sline = e->sline;
-    p.wimg = e->d_wimg;
-    p.pcache = e->pcache;
-    p.scratch = e->d_scratch;
-    p.stood = e->d_stood;
-    p.pnz = e->d_stood ? reinterpret_cast<uint2 *>(e->d_stood + (size_t)e->N * 32u) : nullptr;
-    p.wrec_k = e->tuning.wrec_k;   // launches of at most this many steps write the window record
-    return p;
-}
 
 // The deferred obs flush (env_kernel's DFL): step launches of more than one
 // step with every wave full, in the kernel modes VnTuning::dflush enables
@@ -2102,634 +1977,116 @@ int launch_ph(int N, hipStream_t s, const Params &p) {
     const bool fast = p.reward && p.term && p.trunc && !p.actions_out;
     constexpr bool CAP = pcm_dfl_capable(PCM);
     const bool dfl = CAP && !RESET_ONLY && use_dfl(PCM, N, p.K, p.dflush);
-    const Params &pl = p;
     if (RESET_ONLY)
-        hipLaunchKernelGGL((env_kernel<PH, false, false, true, PCM>), grid, block, 0, s, pl);
+        hipLaunchKernelGGL((env_kernel<PH, false, false, true, PCM>), grid, block, 0, s, p);
     else if (p.actions && fast)
-        hipLaunchKernelGGL((env_kernel<PH, true, true, false, PCM>), grid, block, 0, s, pl);
+        hipLaunchKernelGGL((env_kernel<PH, true, true, false, PCM>), grid, block, 0, s, p);
     else if (p.actions)
-        hipLaunchKernelGGL((env_kernel<PH, true, false, false, PCM>), grid, block, 0, s, pl);
+        hipLaunchKernelGGL((env_kernel<PH, true, false, false, PCM>), grid, block, 0, s, p);
     else if (fast && dfl)
-        hipLaunchKernelGGL((env_kernel<PH, false, true, false, PCM, CAP>), grid, block, 0, s, pl);
+        hipLaunchKernelGGL((env_kernel<PH, false, true, false, PCM, CAP>), grid, block, 0, s, p);
     else if (fast)
-        hipLaunchKernelGGL((env_kernel<PH, false, true, false, PCM>), grid, block, 0, s, pl);
+        hipLaunchKernelGGL((env_kernel<PH, false, true, false, PCM>), grid, block, 0, s, p);
     else if (dfl)
-        hipLaunchKernelGGL((env_kernel<PH, false, false, false, PCM, CAP>), grid, block, 0, s, pl);
+        hipLaunchKernelGGL((env_kernel<PH, false, false, false, PCM, CAP>), grid, block, 0, s, p);
     else
-        hipLaunchKernelGGL((env_kernel<PH, false, false, false, PCM>), grid, block, 0, s, pl);
+        hipLaunchKernelGGL((env_kernel<PH, false, false, false, PCM>), grid, block, 0, s, p);
     VN_HIP(hipGetLastError());
     return VN_OK;
 }
 
-// The kernel mode of a CubicEnv: PCM 1/2 plane sets (PH 8, VnEnv::pcache),
-// PCM 3 byte marks with deferred plane marks (rows of <= 2 words, VnEnv::defer),
+// The kernel mode of a CubicEnv: PCM 1/2 plane sets (PH 8, EnvLayout::pcache),
+// PCM 3 byte marks with deferred plane marks (rows of <= 2 words, EnvLayout::defer),
 // else PCM 0.
-static int env_pcm(const VnEnv *e) {
-    if (e->ph == 8 && e->pcache) return e->pcache;
-    return e->defer ? 3 : 0;
+static int env_pcm(int ph, int pcache, int defer) {
+    if (ph == 8 && pcache) return pcache;
+    return defer ? 3 : 0;
 }
 
 template <bool RESET_ONLY>
-int launch_pcm(VnEnv *e, int pcm, const Params &p, hipStream_t s);
+int launch_pcm(int pcm, const Params &p, hipStream_t s) {
+    if (p.ph == 8) {
+        if (pcm == 2) return launch_ph<8, RESET_ONLY, 2>(p.N, s, p);
+        if (pcm == 1) return launch_ph<8, RESET_ONLY, 1>(p.N, s, p);
+        if (pcm == 3) return launch_ph<8, RESET_ONLY, 3>(p.N, s, p);
+        return launch_ph<8, RESET_ONLY, 0>(p.N, s, p);
+    }
+    if (p.ph == 16)
+        return pcm == 3 ? launch_ph<16, RESET_ONLY, 3>(p.N, s, p) : launch_ph<16, RESET_ONLY, 0>(p.N, s, p);
+    return pcm == 3 ? launch_ph<32, RESET_ONLY, 3>(p.N, s, p) : launch_ph<32, RESET_ONLY, 0>(p.N, s, p);
+}
 
-template <bool RESET_ONLY>
-int launch_env(VnEnv *e, const Params &p, hipStream_t s) {
-    if (e->variant == VN_VARIANT_SIMPLE)
-        return vn_simple::launch(RESET_ONLY, e->sline, e->sbits, e->cfg.local_map_length, e->N, e->obs_dim, &p, s);
-    const int pcm = env_pcm(e);
+}  // namespace
+
+namespace vn_cubic {
+
+int ensure_mt(int device) { return ensure_mt_table(device); }
+
+int launch(bool reset_only, int defer, int wrec_early, bool *wrec_written, const void *params, hipStream_t s) {
+    Params p = *static_cast<const Params *>(params);
+    const int pcm = env_pcm(p.ph, p.pcache, defer);
+    if (reset_only) {
+        *wrec_written = false;
+        return launch_pcm<true>(pcm, p, s);
+    }
     // the window records (wrec_fill): written by step launches of at most
     // wrec_k steps, loaded beside the state when the previous launch wrote them
     // (VnTuning::wrec_early: instead of after it, one dependent round trip less)
-    Params pw = p;
-    if (!RESET_ONLY) {
-        if (p.K <= p.wrec_k) pw.prio |= PRIO_WREC_SAVE;
-        if (e->wrec_written && e->tuning.wrec_early) pw.prio |= PRIO_WREC_EARLY;
-    }
-    e->wrec_written = !RESET_ONLY && p.K <= p.wrec_k;
-    return launch_pcm<RESET_ONLY>(e, pcm, pw, s);
+    if (p.K <= p.wrec_k) p.prio |= PRIO_WREC_SAVE;
+    if (*wrec_written && wrec_early) p.prio |= PRIO_WREC_EARLY;
+    *wrec_written = p.K <= p.wrec_k;
+    return launch_pcm<false>(pcm, p, s);
 }
 
-template <bool RESET_ONLY>
-int launch_pcm(VnEnv *e, int pcm, const Params &p, hipStream_t s) {
-    if (e->ph == 8) {
-        if (pcm == 2) return launch_ph<8, RESET_ONLY, 2>(e->N, s, p);
-        if (pcm == 1) return launch_ph<8, RESET_ONLY, 1>(e->N, s, p);
-        if (pcm == 3) return launch_ph<8, RESET_ONLY, 3>(e->N, s, p);
-        return launch_ph<8, RESET_ONLY, 0>(e->N, s, p);
-    }
-    if (e->ph == 16)
-        return pcm == 3 ? launch_ph<16, RESET_ONLY, 3>(e->N, s, p) : launch_ph<16, RESET_ONLY, 0>(e->N, s, p);
-    return pcm == 3 ? launch_ph<32, RESET_ONLY, 3>(e->N, s, p) : launch_ph<32, RESET_ONLY, 0>(e->N, s, p);
-}
-
-// The kernel instantiation launch_env picks for a call shape (diagnostics /
-// bench labels); kept next to launch_env so the two selections agree.
-std::string kernel_label(const VnEnv *e, bool reset_only, bool ext, bool fast, int k_steps) {
+// The kernel instantiation launch picks for a call shape of p.K steps
+// (diagnostics / bench labels); kept next to launch so the two selections agree.
+std::string label(bool reset_only, bool ext, bool fast, int defer, const void *params) {
+    const Params &p = *static_cast<const Params *>(params);
     char buf[160];
-    if (e->variant == VN_VARIANT_SIMPLE)
-        return vn_simple::label(reset_only, ext, e->sline, e->sbits, e->cfg.local_map_length);
-    const int pcm = env_pcm(e);
+    const int pcm = env_pcm(p.ph, p.pcache, defer);
     const bool x = !reset_only && ext, f = !reset_only && fast;
-    const bool dfl = !reset_only && !x && use_dfl(pcm, e->N, k_steps, e->tuning.dflush);
-    std::snprintf(buf, sizeof(buf), "env_kernel<%d, %s, %s, %s, %d%s>", e->ph, x ? "true" : "false",
+    const bool dfl = !reset_only && !x && use_dfl(pcm, p.N, p.K, p.dflush);
+    std::snprintf(buf, sizeof(buf), "env_kernel<%d, %s, %s, %s, %d%s>", p.ph, x ? "true" : "false",
                   f ? "true" : "false", reset_only ? "true" : "false", pcm, dfl ? ", true" : "");
     return buf;
 }
 
-void free_env(VnEnv *e) {
-    if (!e) return;
-    (void)hipFree(e->d_rooms);
-    (void)hipFree(e->d_rays);
-    (void)hipFree(e->d_starts);
-    (void)hipFree(e->d_lut);
-    (void)hipFree(e->d_hot);
-    (void)hipFree(e->d_seed);
-    (void)hipFree(e->belief_alloc);
-    (void)hipFree(e->d_err);
-    (void)hipFree(e->d_envc);
-    (void)hipFree(e->d_goal);
-    (void)hipFree(e->d_predraw);
-    (void)hipFree(e->d_wimg);
-    (void)hipFree(e->d_stood);
-    (void)hipFree(e->d_scratch);
-    delete e;
-}
-
-// the defaults of every VnTuning field, here only (vn_tuning_default)
-constexpr VnTuning kTuningDefault = {/*pcache_cap*/ -1, /*defer*/ -1, /*simple_layout*/ 0, /*prio*/ 67,
-                                     /*dflush*/ VN_DFLUSH_DEFAULT, /*wrec_k*/ VN_WREC_K_DEFAULT, /*wrec_early*/ 1};
-constexpr int PRIO_USER_BITS = 1 | 2 | 64;   // what env_kernel decodes of VnTuning::prio (the host adds PRIO_WREC_*)
-
-int check_tuning(const VnTuning &t) {
-    if (t.pcache_cap < -1 || t.pcache_cap > 2)
-        return fail(VN_ERR_INVALID, "tuning.pcache_cap must be -1, 0, 1 or 2 (got %d)", t.pcache_cap);
-    if (t.defer != -1 && t.defer != 0) return fail(VN_ERR_INVALID, "tuning.defer must be -1 or 0 (got %d)", t.defer);
-    if (t.simple_layout < 0 || t.simple_layout > 2)
-        return fail(VN_ERR_INVALID, "tuning.simple_layout must be 0, 1 or 2 (got %d)", t.simple_layout);
-    if (t.prio & ~PRIO_USER_BITS)
-        return fail(VN_ERR_INVALID, "tuning.prio must be a subset of bits %d (got %d)", PRIO_USER_BITS, t.prio);
-    if (t.dflush < 0 || t.dflush > 3) return fail(VN_ERR_INVALID, "tuning.dflush must be in 0..3 (got %d)", t.dflush);
-    if (t.wrec_k < 0) return fail(VN_ERR_INVALID, "tuning.wrec_k must be >= 0 (got %d)", t.wrec_k);
-    if (t.wrec_early != 0 && t.wrec_early != 1)
-        return fail(VN_ERR_INVALID, "tuning.wrec_early must be 0 or 1 (got %d)", t.wrec_early);
-    return VN_OK;
-}
-
-// the process options by VN_OPT_* index: values 0..max, and (below) the defaults
-constexpr int32_t kOptionMax[vn_detail::N_OPTIONS] = {2, 1, 1, 1};
-
-}  // namespace
-
-std::atomic<int32_t> vn_detail::g_options[vn_detail::N_OPTIONS] = {{0}, {1}, {1}, {0}};
-
-extern "C" {
-
-const char *vn_last_error(void) { return g_last_error.c_str(); }
-
-int vn_abi_version(void) { return VN_ABI_VERSION; }
-
-int vn_set_option(int32_t option, int32_t value) {
-    if (option < 0 || option >= vn_detail::N_OPTIONS) return fail(VN_ERR_INVALID, "unknown option %d", option);
-    if (value < 0 || value > kOptionMax[option])
-        return fail(VN_ERR_INVALID, "option %d takes 0..%d (got %d)", option, kOptionMax[option], value);
-    vn_detail::g_options[option].store(value, std::memory_order_relaxed);
-    return VN_OK;
-}
-
-int vn_get_option(int32_t option, int32_t *value) {
-    if (!value) return fail(VN_ERR_INVALID, "NULL argument");
-    if (option < 0 || option >= vn_detail::N_OPTIONS) return fail(VN_ERR_INVALID, "unknown option %d", option);
-    *value = vn_detail::option(option);
-    return VN_OK;
-}
-
-int vn_tuning_default(VnTuning *out) {
-    if (!out) return fail(VN_ERR_INVALID, "NULL argument");
-    *out = kTuningDefault;
-    return VN_OK;
-}
-
-int vn_set_tuning(VnEnv *env, const VnTuning *tuning) {
-    if (!env || !tuning) return fail(VN_ERR_INVALID, "NULL argument");
-    if (const int rc = check_tuning(*tuning)) return rc;
-    const VnTuning &cur = env->tuning;
-    if (tuning->pcache_cap != cur.pcache_cap)
-        return fail(VN_ERR_INVALID, "tuning.pcache_cap is fixed at creation (%d, got %d)", cur.pcache_cap, tuning->pcache_cap);
-    if (tuning->defer != cur.defer)
-        return fail(VN_ERR_INVALID, "tuning.defer is fixed at creation (%d, got %d)", cur.defer, tuning->defer);
-    if (tuning->simple_layout != cur.simple_layout)
-        return fail(VN_ERR_INVALID, "tuning.simple_layout is fixed at creation (%d, got %d)", cur.simple_layout,
-                    tuning->simple_layout);
-    env->tuning = *tuning;
-    return VN_OK;
-}
-
-int vn_create(const VnRoomSet *rooms, int32_t n_agents, const VnConfig *cfg, int32_t device, VnEnv **out) {
-    return vn_create_tuned(rooms, n_agents, cfg, device, nullptr, out);
-}
-
-int vn_create_tuned(const VnRoomSet *rooms, int32_t n_agents, const VnConfig *cfg, int32_t device,
-                    const VnTuning *tuning, VnEnv **out) {
-    if (!rooms || !cfg || !out) return fail(VN_ERR_INVALID, "NULL argument");
-    *out = nullptr;
-    const VnTuning tun = tuning ? *tuning : kTuningDefault;
-    if (const int rc = check_tuning(tun)) return rc;
-    if (n_agents <= 0) return fail(VN_ERR_INVALID, "n_agents must be > 0 (got %d)", n_agents);
-    if (rooms->n_rooms <= 0 || rooms->n_rooms > VN_MAX_ROOMS)
-        return fail(VN_ERR_INVALID, "n_rooms must be in 1..%d (got %d)", VN_MAX_ROOMS, rooms->n_rooms);
-    if (!rooms->whd || !rooms->walls) return fail(VN_ERR_INVALID, "rooms->whd / rooms->walls is NULL");
-    if (cfg->local_map_length < 1 || cfg->local_map_length > VN_MAX_L)
-        return fail(VN_ERR_INVALID, "local_map_length must be in 1..%d (got %d)", VN_MAX_L, cfg->local_map_length);
-    if (cfg->variant != VN_VARIANT_CUBIC && cfg->variant != VN_VARIANT_SIMPLE)
-        return fail(VN_ERR_INVALID, "variant must be %d (CubicEnv) or %d (simpleEnv), got %d", VN_VARIANT_CUBIC,
-                    VN_VARIANT_SIMPLE, cfg->variant);
-
-    // ---- rooms -> descriptors, ray records, start lists ----
-    const int nr = rooms->n_rooms;
-    std::vector<uint32_t> desc((size_t)nr * 8, 0);
-    std::vector<uint2> rays;
-    std::vector<uint32_t> starts;
-    std::vector<uint32_t> total_free(nr);
-    int maxW = 0, maxD = 0, maxH = 0;
-    size_t woff = 0;
-    for (int r = 0; r < nr; ++r) {
-        const int W = rooms->whd[3 * r], D = rooms->whd[3 * r + 1], H = rooms->whd[3 * r + 2];
-        if (W < 1 || W > VN_MAX_W || D < 1 || D > VN_MAX_D || H < 1 || H > VN_MAX_H)
-            return fail(VN_ERR_ROOM, "room %d: size %dx%dx%d outside 1..%d x 1..%d x 1..%d", r, W, D, H, VN_MAX_W,
-                        VN_MAX_D, VN_MAX_H);
-        const uint8_t *wall = rooms->walls + woff;
-        auto is_wall = [&](int x, int y, int z) { return wall[((size_t)x * D + y) * H + z] != 0; };
-        const uint32_t ray_off = (uint32_t)rays.size(), start_off = (uint32_t)starts.size();
-        // interior scan in x -> y -> z order (envs/CubicEnv.py:450-457)
-        uint32_t tf = 0;
-        for (int x = 1; x < W - 1; ++x)
-            for (int y = 1; y < D - 1; ++y)
-                for (int z = 1; z < H - 1; ++z)
-                    if (!is_wall(x, y, z)) {
-                        starts.push_back((uint32_t)x | ((uint32_t)y << 8) | ((uint32_t)z << 16));
-                        ++tf;
-                    }
-        if (tf == 0) return fail(VN_ERR_ROOM, "room %d has no interior free cell (random.choice of [])", r);
-        total_free[r] = tf;
-        // ray records
-        static const int DX[6] = {1, -1, 0, 0, 0, 0}, DY[6] = {0, 0, 1, -1, 0, 0}, DZ[6] = {0, 0, 0, 0, 1, -1};
-        for (int x = 0; x < W; ++x)
-            for (int y = 0; y < D; ++y)
-                for (int z = 0; z < H; ++z) {
-                    uint32_t e8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-                    for (int d = 0; d < 6; ++d) {
-                        int n = 0;
-                        uint32_t wf = 0;
-                        for (int s = 1;; ++s) {
-                            const int nx = x + DX[d] * s, ny = y + DY[d] * s, nz = z + DZ[d] * s;
-                            if (nx < 0 || nx >= W || ny < 0 || ny >= D || nz < 0 || nz >= H) break;
-                            if (is_wall(nx, ny, nz)) {
-                                wf = 1;
-                                break;
-                            }
-                            ++n;
-                        }
-                        if (n > 127) {
-                            n = 127;
-                            wf = 0;
-                        }
-                        e8[d] = (uint32_t)n | (wf << 7);
-                    }
-                    e8[6] = is_wall(x, y, z) ? 1u : 0u;
-                    uint2 rec;
-                    rec.x = e8[0] | (e8[1] << 8) | (e8[2] << 16) | (e8[3] << 24);
-                    rec.y = e8[4] | (e8[5] << 8) | (e8[6] << 16);
-                    // bit 17: some ray from this cell ends at the room's edge (not a
-                    // wall), i.e. may take the edge-quirk mark (simple_pipe_kernel)
-                    for (int d = 0; d < 6; ++d)
-                        if (!(e8[d] & 0x80u) && (e8[d] & 0x7fu) >= 1u && (e8[d] & 0x7fu) < 127u) rec.y |= 1u << 17;
-                    rays.push_back(rec);
-                }
-        int32_t fixed = -1;
-        if (rooms->fixed_start && rooms->fixed_start[3 * r] >= 0) {
-            const int sx = rooms->fixed_start[3 * r], sy = rooms->fixed_start[3 * r + 1],
-                      sz = rooms->fixed_start[3 * r + 2];
-            if (sx >= W || sy < 0 || sy >= D || sz < 0 || sz >= H)
-                return fail(VN_ERR_ROOM, "room %d: start position (%d,%d,%d) outside the room", r, sx, sy, sz);
-            fixed = sx | (sy << 8) | (sz << 16);
-        }
-        int32_t fgoal = -1;
-        if (rooms->goal && rooms->goal[3 * r] >= 0) {
-            const int gx = rooms->goal[3 * r], gy = rooms->goal[3 * r + 1], gz = rooms->goal[3 * r + 2];
-            if (gx >= W || gy < 0 || gy >= D || gz < 0 || gz >= H)
-                return fail(VN_ERR_ROOM, "room %d: goal (%d,%d,%d) outside the room", r, gx, gy, gz);
-            fgoal = gx | (gy << 8) | (gz << 16);
-        }
-        uint32_t *d = &desc[(size_t)r * 8];
-        d[0] = (uint32_t)W | ((uint32_t)D << 8) | ((uint32_t)H << 16);
-        d[1] = tf;
-        d[2] = ray_off;
-        d[3] = start_off;
-        d[4] = (uint32_t)fixed;
-        d[5] = (uint32_t)((W + 3) / 4) | ((uint32_t)((D + 3) / 4) << 16);
-        {   // done <=> visited / total >= finish in f64 (CubicEnv.py:212-213); monotone in visited
-            const double fin = cfg->finish_percentage == 0.0 ? 0.84 : cfg->finish_percentage;
-            uint32_t v = 0;
-            const uint32_t vmax = (uint32_t)W * D * H + 1;
-            while (v < vmax && !((double)v / (double)tf >= fin)) ++v;
-            d[6] = v;
-        }
-        d[7] = (uint32_t)fgoal;
-        maxW = W > maxW ? W : maxW;
-        maxD = D > maxD ? D : maxD;
-        maxH = H > maxH ? H : maxH;
-        woff += (size_t)W * D * H;
-    }
-
-    VnEnv *e = new (std::nothrow) VnEnv();
-    if (!e) return fail(VN_ERR_OOM, "host allocation failed");
-    e->device = device;
-    e->N = n_agents;
-    e->cfg = *cfg;
-    e->tuning = tun;
-    if (e->cfg.finish_percentage == 0.0) e->cfg.finish_percentage = 0.84;
-    if (e->cfg.seed_stride == 0) e->cfg.seed_stride = n_agents;
-    e->n_rooms = nr;
-    e->total_free = total_free;
-    // timing diagnostics only; every ablation keeps all addresses inside the
-    // agent's room (bits: 1 entering-column loads, 2 plane rows and blind marks,
-    // 4 obs rows, 8 column write-backs, 16 obs flush to HBM, 32 plane word writes
-    // and blind marks; 2 skips the plane row loads)
-    e->variant = cfg->variant;
-    e->obs_dim = cfg->variant == VN_VARIANT_SIMPLE ? 6 * cfg->local_map_length + 7 : VN_OBS_DIM;
-    e->nbx = (maxW + 3) / 4;
-    e->nby = (maxD + 3) / 4;
-    e->ph = maxH <= 8 ? 8 : maxH <= 16 ? 16 : 32;   // whole column = one 8/16/32-byte access
-    const bool dense = tun.simple_layout == 2;   // force the dense kernel (tests)
-    if (e->variant == VN_VARIANT_SIMPLE && maxW <= 64 && maxD <= 64 && !dense) {
-        // bit planes: SX u64 [pd][ph], SY u64 [pw][ph], SZ u32 [pw][pd], QZ u32 [pw][pd]
-        e->sbits = 1;
-        e->pw = maxW;
-        e->pd = maxD;
-        e->map_bytes = 0;
-        e->nwx = e->nwy = 0;
-        // A/B knob: simple_layout 1 keeps the word layout
-        e->sline = (maxW <= 32 && maxD <= 32 && e->ph == 8 && tun.simple_layout != 1) ? 1 : 0;
-        if (e->sline) {
-            // lines: SX u32 [pd][8] (bit x), SY u32 [pw][8] (bit y), QZ u32 [pw][pd]
-            e->sy_off = (uint32_t)(32 * e->pd);
-            e->sz_off = e->sy_off + (uint32_t)(32 * e->pw);   // (no SZ copy)
-            e->qz_off = e->sz_off;
-            e->agent_bytes = (e->qz_off + (uint32_t)(4 * e->pw * e->pd) + 63u) & ~63u;
-        } else {
-            e->sy_off = (uint32_t)(8 * e->pd * e->ph);
-            e->sz_off = e->sy_off + (uint32_t)(8 * e->pw * e->ph);
-            e->qz_off = e->sz_off + (uint32_t)(4 * e->pw * e->pd);
-            e->agent_bytes = (e->qz_off + (uint32_t)(4 * e->pw * e->pd) + 15u) & ~15u;
-        }
-        e->xp_off = e->yp_off = 0;
-    } else if (e->variant == VN_VARIANT_SIMPLE) {
-        // dense [pw][pd][ph] int8 map, no planes
-        e->pw = maxW;
-        e->pd = maxD;
-        e->map_bytes = (uint32_t)(e->pw * e->pd * e->ph);
-        e->nwx = e->nwy = 0;
-        e->xp_off = e->yp_off = e->map_bytes;
-        e->agent_bytes = (e->map_bytes + 15u) & ~15u;
-    } else {
-        e->pw = e->nbx * 4;
-        e->pd = e->nby * 4;
-        e->map_bytes = (uint32_t)(e->nbx * e->nby * 16 * e->ph);
-        e->nwx = (e->pw + 63) / 64;
-        e->nwy = (e->pd + 63) / 64;
-        // plane-set mode: 2 = u32 rows (rooms <= 32 x 32), 1 = u64 rows (<= 64 x 64), 0 = byte marks
-        e->pcache = e->ph != 8 ? 0 : (e->pw <= 32 && e->pd <= 32) ? 2 : (e->nwx == 1 && e->nwy == 1) ? 1 : 0;
-        // A/B knob pcache_cap: 0 off, 1 at most u64 rows
-        if (tun.pcache_cap >= 0 && tun.pcache_cap < e->pcache) e->pcache = tun.pcache_cap;
-        // byte-mark mode with plane rows of <= 2 words: defer each pass's plane marks
-        // to the next step (PendMarks) so the row loads hide behind a step
-        // (A/B knob defer: 0 marks in the sensing pass)
-        e->defer = (e->pcache == 0 && e->nwx <= 2 && e->nwy <= 2 && tun.defer != 0) ? 1 : 0;
-        const int rowb = e->pcache == 2 ? 4 : 8;                            // plane row bytes
-        e->xp_off = e->map_bytes;                                           // rows (y, z): pd * ph * nwx words
-        e->yp_off = e->xp_off + (uint32_t)(e->pd * e->ph * e->nwx * rowb);  // rows (x, z): pw * ph * nwy words
-        e->agent_bytes = (e->yp_off + (uint32_t)(e->pw * e->ph * e->nwy * rowb) + 15u) & ~15u;
-        e->plane_bytes = e->agent_bytes - e->xp_off;
-#ifdef VN_DIAG
-        // placement study (diagnostics build): VOXNAV_AGENT_PAD extra bytes of per-agent stride
-        if (const char *ap = getenv("VOXNAV_AGENT_PAD")) e->agent_bytes += ((uint32_t)atoi(ap) + 15u) & ~15u;
-#endif
-    }
-
-    DeviceGuard dg(device);
-    int rc = ensure_mt_table(device);
-    if (!rc) rc = vn_simple::ensure_mt(device);
-    if (rc) {
-        delete e;
-        return rc;
-    }
-    // LDS table (TAB_SIZE floats): obs value of every belief byte (decode,
-    // clip to [-2, 20], (v + 2) / 22 in IEEE f32 -- :273-275), f32(a / 5.0)
-    // (:284) and f32(c / L) (:287), all computed on the host.
-    float lut[TAB_ALL];
-    for (int k = 0; k < TAB_ALL; ++k) lut[k] = 0.0f;
-    for (int ev = 0; ev < 16; ++ev) {   // simpleEnv compute_reward (:189-217) by event code, in its order
-        volatile double r = -0.1;
-        if (ev & 1) r = r + -10.0;
-        if (ev & 2) r = r + 0.05;
-        if (ev & 4) r = r + 100.0;
-        if (ev & 8) r = r + 1.0;        // (the truncation term adds 0.0: no change)
-        const double rv = r;
-        lut[TAB_SREW + ev] = (float)rv;
-        std::memcpy(&lut[TAB_SREW64 + 2 * ev], &rv, sizeof(double));
-    }
-    for (int b = 0; b < 256; ++b) {
-        int v = (b & 0x80) ? ((b & 0x40) ? -2 : (b & 0x3f)) : -1;
-        if (v > 20) v = 20;
-        volatile float num = (float)(v + 2);
-        lut[b] = num / 22.0f;
-    }
-    // plane-set staging codes (bytes no belief cell holds): tail values
-    lut[TC_ZERO] = 0.0f;
-    lut[TC_ONE] = 1.0f;
-    for (int a = 0; a < 6; ++a) lut[TC_ACT + a] = (float)((double)a / 5.0);
-    for (int c = 0; c <= cfg->local_map_length; ++c)
-        lut[TC_CID + c] = (float)((double)c / (double)cfg->local_map_length);
-    for (int a = 0; a < 6; ++a) lut[TAB_ACTION + a] = (float)((double)a / 5.0);
-    for (int c = 0; c <= cfg->local_map_length; ++c)
-        lut[TAB_CID + c] = (float)((double)c / (double)cfg->local_map_length);
-    const size_t belief_bytes = (size_t)e->agent_bytes * (size_t)n_agents;
-#define VN_ALLOC(ptr, bytes)                                                                    \
-    do {                                                                                        \
-        hipError_t e_ = hipMalloc((void **)&(ptr), (bytes));                                    \
-        if (e_ != hipSuccess) {                                                                 \
-            free_env(e);                                                                        \
-            return fail(VN_ERR_OOM, "hipMalloc(%zu) failed: %s", (size_t)(bytes), hipGetErrorString(e_)); \
-        }                                                                                       \
-        e->device_bytes += (bytes);                                                             \
-    } while (0)
-    VN_ALLOC(e->d_rooms, desc.size() * sizeof(uint32_t));
-    VN_ALLOC(e->d_rays, rays.size() * sizeof(uint2));
-    VN_ALLOC(e->d_starts, starts.size() * sizeof(uint32_t));
-    VN_ALLOC(e->d_lut, sizeof(lut));
-    // the hot state, then (CubicEnv) the window records: 16 columns x PH bytes per agent (wrec_base)
-    VN_ALLOC(e->d_hot, (size_t)n_agents * (sizeof(uint4) + (e->variant != VN_VARIANT_SIMPLE ? 16u * (size_t)e->ph : 0u)));
-    VN_ALLOC(e->d_seed, (size_t)n_agents * sizeof(uint32_t));
-    {
-        // The belief maps.  A VMM-mapped variant (hipMemCreate / hipMemMap
-        // chunks) was measured in round 6 and removed: on that memory the
-        // kernels' results differed from the oracle, and it did not remove the
-        // P-set kernels' trial-to-trial swing.  The cause of the
-        // mismatch is not identified: the logs show marks written by one launch
-        // not seen by the first step of the next (Weak #1).
-        size_t off = 0;
-        bool contig = false;
-#ifdef VN_DIAG
-        // placement study (diagnostics build): VOXNAV_BELIEF_OFFSET bytes into
-        // the allocation; VOXNAV_BELIEF_CONTIG=1 a physically contiguous
-        // allocation (hipDeviceMallocContiguous)
-        if (const char *bo = getenv("VOXNAV_BELIEF_OFFSET")) off = (((size_t)atoll(bo)) + 255u) & ~(size_t)255u;
-        const char *bc = getenv("VOXNAV_BELIEF_CONTIG");
-        contig = bc && bc[0] == '1';
-#endif
-        e->belief_alloc_bytes = belief_bytes + off;
-        if (contig) {
-            const hipError_t ce = hipExtMallocWithFlags(&e->belief_alloc, e->belief_alloc_bytes, hipDeviceMallocContiguous);
-            if (ce != hipSuccess) {
-                free_env(e);
-                return fail(VN_ERR_OOM, "hipExtMallocWithFlags(%zu, contiguous) failed: %s", e->belief_alloc_bytes,
-                            hipGetErrorString(ce));
-            }
-            e->device_bytes += e->belief_alloc_bytes;
-        } else {
-            VN_ALLOC(e->belief_alloc, e->belief_alloc_bytes);
-        }
-        e->d_belief = reinterpret_cast<int8_t *>(e->belief_alloc) + off;
-    }
-    VN_ALLOC(e->d_err, sizeof(int32_t));
-    VN_ALLOC(e->d_envc, sizeof(EnvConst));
-    VN_ALLOC(e->d_goal, (size_t)n_agents * sizeof(uint32_t));
-    VN_ALLOC(e->d_predraw, (size_t)n_agents * sizeof(uint4));
-    if (e->pcache) VN_ALLOC(e->d_wimg, (size_t)nr * VN_WIMG_REP * e->map_bytes);
-    if (e->pcache == 2) VN_ALLOC(e->d_stood, (size_t)n_agents * 34u * sizeof(uint32_t));
-    VN_ALLOC(e->d_scratch, 8192);
-#undef VN_ALLOC
-    hipError_t he = hipSuccess;
-    if (he == hipSuccess) he = hipMemcpy(e->d_rooms, desc.data(), desc.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMemcpy(e->d_rays, rays.data(), rays.size() * sizeof(uint2), hipMemcpyHostToDevice);
-    if (he == hipSuccess)
-        he = hipMemcpy(e->d_starts, starts.data(), starts.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMemcpy(e->d_lut, lut, sizeof(lut), hipMemcpyHostToDevice);
-    if (he == hipSuccess) he = hipMemset(e->d_hot, 0, (size_t)n_agents * sizeof(uint4));
-    if (he == hipSuccess) he = hipMemset(e->d_seed, 0, (size_t)n_agents * sizeof(uint32_t));
-    // unknown: 0x00 in the CubicEnv byte encoding, -1 (0xFF) in the dense simpleEnv map; empty bit planes
-    if (he == hipSuccess) he = hipMemset(e->d_belief, e->variant == VN_VARIANT_SIMPLE && !e->sbits ? 0xFF : 0x00, belief_bytes);
-    if (he == hipSuccess) he = hipMemset(e->d_goal, 0, (size_t)n_agents * sizeof(uint32_t));
-    if (he == hipSuccess) he = hipMemset(e->d_predraw, 0, (size_t)n_agents * sizeof(uint4));
-    if (he == hipSuccess) he = hipMemset(e->d_err, 0, sizeof(int32_t));
-    if (he == hipSuccess && e->d_stood) he = hipMemset(e->d_stood, 0, (size_t)n_agents * 34u * sizeof(uint32_t));
-    if (he == hipSuccess && e->pcache) {
-        // per room: the bricked byte map of a fresh episode -- 0x40 (latent
-        // wall, still unknown) at every wall cell, 0 elsewhere
-        std::vector<int8_t> img((size_t)nr * VN_WIMG_REP * e->map_bytes, 0);
-        size_t wo = 0;
-        for (int r = 0; r < nr; ++r) {
-            const int W = rooms->whd[3 * r], D = rooms->whd[3 * r + 1], H = rooms->whd[3 * r + 2];
-            int8_t *m = img.data() + (size_t)r * VN_WIMG_REP * e->map_bytes;
-            for (int x = 0; x < W; ++x)
-                for (int y = 0; y < D; ++y)
-                    for (int z = 0; z < H; ++z)
-                        if (rooms->walls[wo + ((size_t)x * D + y) * H + z])
-                            m[bcol(x, y, e->nby) * (size_t)e->ph + z] = 0x40;
-            wo += (size_t)W * D * H;
-            for (int c = 1; c < VN_WIMG_REP; ++c) std::memcpy(m + (size_t)c * e->map_bytes, m, e->map_bytes);
-        }
-        he = hipMemcpy(e->d_wimg, img.data(), img.size(), hipMemcpyHostToDevice);
-    }
-    if (he == hipSuccess) {
-        EnvConst ec;
-        std::memset(&ec, 0, sizeof(ec));
-        ec.rooms = e->d_rooms;
-        ec.rays = e->d_rays;
-        ec.starts = e->d_starts;
-        ec.err = e->d_err;
-        ec.n_rooms = e->n_rooms;
-        ec.use_room_draw = e->cfg.use_room_draw;
-        ec.nby = e->nby;
-        ec.agent_bytes = e->agent_bytes;
-        ec.xp_off = e->xp_off;
-        ec.map_bytes = e->map_bytes;
-        ec.plane_bytes = e->plane_bytes;
-        ec.pcache = e->pcache;
-        ec.wimg = reinterpret_cast<const uint4 *>(e->d_wimg);
-        he = hipMemcpy(e->d_envc, &ec, sizeof(ec), hipMemcpyHostToDevice);
-    }
-    if (he == hipSuccess) he = hipDeviceSynchronize();
-    if (he != hipSuccess) {
-        free_env(e);
-        return fail(VN_ERR_HIP, "vn_create upload: %s", hipGetErrorString(he));
-    }
-    *out = e;
-    return VN_OK;
-}
-
-int vn_destroy(VnEnv *env) {
-    if (!env) return VN_OK;
-    DeviceGuard dg(env->device);
-    (void)hipDeviceSynchronize();
-    free_env(env);
-    return VN_OK;
-}
-
-int vn_get_info(const VnEnv *env, VnInfo *info) {
-    if (!env || !info) return fail(VN_ERR_INVALID, "NULL argument");
-    info->n_agents = env->N;
-    info->n_rooms = env->n_rooms;
-    info->local_map_length = env->cfg.local_map_length;
-    info->pad_w = env->pw;
-    info->pad_d = env->pd;
-    info->pad_h = env->ph;
-    info->belief_bytes_per_agent = env->agent_bytes;
-    info->device_bytes = (int64_t)env->device_bytes;
-    info->variant = env->variant;
-    info->obs_dim = env->obs_dim;
-    return VN_OK;
-}
-
-int vn_reset(VnEnv *env, const int64_t *seeds, const uint8_t *mask, float *obs, void *stream) {
-    if (!env || !seeds || !obs) return fail(VN_ERR_INVALID, "NULL argument");
-    DeviceGuard dg(env->device);
-    Params p = base_params(env);
-    p.seeds = seeds;
-    p.mask = mask;
-    p.obs = obs;
-    return launch_env<true>(env, p, (hipStream_t)stream);
-}
-
-int vn_step(VnEnv *env, const int32_t *actions, float *obs, float *reward, double *reward64, uint8_t *terminated,
-            uint8_t *truncated, float *terminal_obs, void *stream) {
-    if (!env || !actions || !obs) return fail(VN_ERR_INVALID, "NULL argument");
-    DeviceGuard dg(env->device);
-    Params p = base_params(env);
-    p.K = 1;
-    p.actions = actions;
-    p.obs = obs;
-    p.reward = reward;
-    p.reward64 = reward64;
-    p.term = terminated;
-    p.trunc = truncated;
-    p.terminal_obs = terminal_obs;
-    return launch_env<false>(env, p, (hipStream_t)stream);
-}
-
-int vn_step_random(VnEnv *env, uint64_t policy_seed, uint64_t t0, int32_t k_steps, int32_t *actions_out, float *obs,
-                   float *reward, double *reward64, uint8_t *terminated, uint8_t *truncated, float *terminal_obs,
-                   void *stream) {
-    if (!env || !obs) return fail(VN_ERR_INVALID, "NULL argument");
-    if (k_steps < 1) return fail(VN_ERR_INVALID, "k_steps must be >= 1 (got %d)", k_steps);
-    DeviceGuard dg(env->device);
-    Params p = base_params(env);
-    p.K = k_steps;
-    p.actions = nullptr;
-    p.policy_seed = policy_seed;
-    p.t0 = t0;
-    p.actions_out = actions_out;
-    p.obs = obs;
-    p.reward = reward;
-    p.reward64 = reward64;
-    p.term = terminated;
-    p.trunc = truncated;
-    p.terminal_obs = terminal_obs;
-    return launch_env<false>(env, p, (hipStream_t)stream);
-}
-
-int vn_kernel_label(const VnEnv *env, int32_t k_steps, int32_t explicit_actions, int32_t fast, char *buf,
-                    int32_t len) {
-    if (!env || !buf || len < 1) return fail(VN_ERR_INVALID, "NULL argument");
-    const std::string s = kernel_label(env, k_steps == 0, explicit_actions != 0, fast != 0, k_steps);
-    std::snprintf(buf, (size_t)len, "%s", s.c_str());
-    return (int)s.size() < len ? VN_OK : fail(VN_ERR_INVALID, "buffer too small (%d)", (int)len);
-}
-
-int vn_export_state(VnEnv *env, int64_t *state_out, void *stream) {
-    if (!env || !state_out) return fail(VN_ERR_INVALID, "NULL argument");
-    DeviceGuard dg(env->device);
-    Params p = base_params(env);
-    hipLaunchKernelGGL(export_state_kernel, dim3((unsigned)((env->N + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)stream, p, state_out);
+int export_state(const void *params, int64_t *out, hipStream_t s) {
+    const Params &p = *static_cast<const Params *>(params);
+    hipLaunchKernelGGL(export_state_kernel, dim3((unsigned)((p.N + 255) / 256)), dim3(256), 0, s, p, out);
     VN_HIP(hipGetLastError());
     return VN_OK;
 }
 
-int vn_export_belief(VnEnv *env, int8_t *belief_out, void *stream) {
-    if (!env || !belief_out) return fail(VN_ERR_INVALID, "NULL argument");
-    DeviceGuard dg(env->device);
-    Params p = base_params(env);
-    if (env->variant == VN_VARIANT_SIMPLE)
-        return vn_simple::export_belief(&p, belief_out, env->pw, env->pd, (hipStream_t)stream);
-    const size_t total = (size_t)env->N * env->pw * env->pd * env->ph;
-    hipLaunchKernelGGL(export_belief_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)stream, p, belief_out, env->pw, env->pd);
+int export_belief(const void *params, int8_t *out, int pw, int pd, hipStream_t s) {
+    const Params &p = *static_cast<const Params *>(params);
+    const size_t total = (size_t)p.N * pw * pd * p.ph;
+    hipLaunchKernelGGL(export_belief_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, p, out, pw, pd);
     VN_HIP(hipGetLastError());
     return VN_OK;
 }
 
-#ifdef VN_DIAG
-// diagnostics build (placement study): the device address of the belief maps and the per-agent stride
-int vn_debug_belief_addr(const VnEnv *env, uint64_t *addr, uint32_t *stride) {
-    if (!env || !addr || !stride) return fail(VN_ERR_INVALID, "NULL argument");
-    *addr = (uint64_t)(uintptr_t)env->d_belief;
-    *stride = env->agent_bytes;
+int gae(const float *rew, const float *val, const float *starts, const float *last_v, const float *dones, int T, int N,
+        float g32, float gl32, float *adv, float *ret, hipStream_t s) {
+    hipLaunchKernelGGL(gae_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, rew, val, starts, last_v, dones,
+                       T, N, g32, gl32, adv, ret);
+    VN_HIP(hipGetLastError());
     return VN_OK;
 }
-#endif
 
+}  // namespace vn_cubic
+
+// diagnostics builds: the profiling exports stay with the device symbols they read
 #if VN_ENV_PROF || VN_ENV_WT
 // the per-wave start / end clocks and ids of the last profiled launch
-int vn_debug_env_wavetimes(unsigned long long *t, unsigned int *ids) {
+extern "C" int vn_debug_env_wavetimes(unsigned long long *t, unsigned int *ids) {
     VN_HIP(hipMemcpyFromSymbol(t, HIP_SYMBOL(g_env_wt), sizeof(unsigned long long) * 8192 * 2));
     VN_HIP(hipMemcpyFromSymbol(ids, HIP_SYMBOL(g_env_wid), sizeof(unsigned int) * 8192 * 2));
     return 0;
 }
 #endif
 #if VN_ENV_PROF
-
-int vn_debug_env_prof(unsigned long long *out16, int clear) {
+extern "C" int vn_debug_env_prof(unsigned long long *out16, int clear) {
     VN_HIP(hipMemcpyFromSymbol(out16, HIP_SYMBOL(g_env_prof), sizeof(unsigned long long) * 16));
     if (clear) {
         unsigned long long z[16] = {0};
@@ -2738,19 +2095,3 @@ int vn_debug_env_prof(unsigned long long *out16, int clear) {
     return 0;
 }
 #endif
-
-int vn_gae(const float *rewards, const float *values, const float *episode_starts, const float *last_values,
-           const float *dones, int32_t T, int32_t N, double gamma, double gae_lambda, float *advantages,
-           float *returns, void *stream) {
-    if (!rewards || !values || !episode_starts || !last_values || !dones || !advantages || !returns)
-        return fail(VN_ERR_INVALID, "NULL argument");
-    if (T < 1 || N < 1) return fail(VN_ERR_INVALID, "T and N must be >= 1 (got %d, %d)", T, N);
-    const float g32 = (float)gamma;
-    const float gl32 = (float)(gamma * gae_lambda);
-    hipLaunchKernelGGL(gae_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rewards,
-                       values, episode_starts, last_values, dones, T, N, g32, gl32, advantages, returns);
-    VN_HIP(hipGetLastError());
-    return VN_OK;
-}
-
-}  // extern "C"

@@ -1,9 +1,9 @@
 // voxnav_simple.hip -- MI355X (gfx950) kernels of the simpleEnv variant
 // (envs/simpleEnv.py).  Split from voxnav_env.hip:
-// the CubicEnv step kernel and the C-ABI stay there; this unit holds the
+// the CubicEnv step kernel stays there (the C-ABI: voxnav_api.hip); this unit holds the
 // simpleEnv step kernels (line layout for rooms <= 32 x 32 x 8, word layout
 // up to 64 x 64 x 31, dense maps beyond), their reset kernel and belief
-// export, and the launcher voxnav_env.hip's launch_env calls.
+// export, and the launcher voxnav_api.hip's launch_env calls (vn_simple).
 
 #include "env_core.h"
 
@@ -1540,7 +1540,7 @@ __global__ void export_belief_simple_kernel(Params p, int8_t *out, int pw, int p
 namespace vn_simple {
 
 // Params crosses the unit boundary as a pointer: each unit has its own
-// (identical) copy of the anonymous-namespace layout from env_core.h.
+// (identical) copy of the anonymous-namespace layout from env_params.h.
 
 int ensure_mt(int device) { return ensure_mt_table(device); }
 
