@@ -2,7 +2,8 @@
 // hands the two kernel units: the launch parameters (Params), the
 // env-constant block the reset path reads from device memory (EnvConst), and
 // the units' host interfaces (vn_cubic: voxnav_env.hip, vn_simple:
-// voxnav_simple.hip).  No device code and no device symbol.  The structs are
+// voxnav_simple.hip, vn_state: voxnav_state.hip).  No device code and no
+// device symbol.  The structs are
 // in an anonymous namespace: each unit has its own (identical) copy, so
 // Params crosses the unit boundary as a pointer.
 #pragma once
@@ -89,6 +90,13 @@ int export_belief(const void *params, int8_t *out, int pw, int pd, hipStream_t s
 int gae(const float *rew, const float *val, const float *starts, const float *last_v, const float *dones, int T, int N,
         float g32, float gl32, float *adv, float *ret, hipStream_t s);
 }  // namespace vn_cubic
+
+// The CubicEnv state import (voxnav_state.hip; the encoder is env_state.h).
+// Zeroes *n_rejected (when given) on the stream, then one launch.
+namespace vn_state {
+int import_state(const void *params, const int64_t *state, const int8_t *belief, const uint8_t *mask, float *obs,
+                 int32_t *n_rejected, int pw, int pd, hipStream_t s);
+}  // namespace vn_state
 
 // The simpleEnv unit (voxnav_simple.hip).
 namespace vn_simple {

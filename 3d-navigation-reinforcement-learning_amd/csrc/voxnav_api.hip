@@ -4,7 +4,9 @@
 // plans on the host (env_plan.h: room tables, EnvLayout, LUT, room images),
 // uploads the result and builds the env's Params once; a call copies that
 // Params, sets its own pointers and hands it to the variant's kernel unit
-// (vn_cubic: voxnav_env.hip, vn_simple: voxnav_simple.hip; env_params.h).
+// (vn_cubic: voxnav_env.hip, vn_simple: voxnav_simple.hip, the state import
+// vn_state: voxnav_state.hip; env_params.h).  The whole-env snapshots are
+// host code here: device-to-device copies of the env's buffers under a tag.
 
 #include <atomic>
 #include <cstdlib>
@@ -62,6 +64,7 @@ struct VnEnv {
     size_t device_bytes = 0;
     Params params{};  // everything but the per-call fields (call_params), built once by vn_create
     bool wrec_written = false;    // the last step launch wrote every agent's window record (wrec_fill)
+    uint64_t snap_tag = 0;        // hash of everything that decides what a snapshot's bytes mean (snapshot_tag)
 
     int alloc(DevBuf &b, size_t bytes) {
         const hipError_t he = hipMalloc(&b.ptr, bytes);
@@ -257,6 +260,66 @@ Params env_params(const VnEnv *e, size_t belief_off) {
     return p;
 }
 
+// ---- whole-env snapshots: every mutable per-agent buffer, in one order ----
+struct SnapPart {
+    void *ptr;
+    size_t bytes;
+};
+
+// hot state with the window records behind it, next seeds, belief blocks,
+// goals, the simpleEnv draw-ahead, stood rows with the nonzero-set masks
+int snap_parts(const VnEnv *e, SnapPart out[6]) {
+    int n = 0;
+    out[n++] = {e->hot.ptr, e->hot.bytes};
+    out[n++] = {e->seed.ptr, e->seed.bytes};
+    out[n++] = {e->params.belief, (size_t)e->lay.agent_bytes * (size_t)e->N};
+    out[n++] = {e->goal.ptr, e->goal.bytes};
+    out[n++] = {e->predraw.ptr, e->predraw.bytes};
+    if (e->stood.ptr) out[n++] = {e->stood.ptr, e->stood.bytes};
+    return n;
+}
+
+constexpr size_t SNAP_ALIGN = 256;   // each part starts on a 256-byte boundary of the blob
+
+// FNV-1a over the values that decide the bytes' meaning: ABI version, variant,
+// N, L, the planned layout, the creation-time tuning, the config and the room
+// tables.  Host arithmetic only.
+struct Fnv {
+    uint64_t h = 1469598103934665603ull;
+    void bytes(const void *p, size_t n) {
+        const unsigned char *c = static_cast<const unsigned char *>(p);
+        for (size_t i = 0; i < n; ++i) h = (h ^ c[i]) * 1099511628211ull;
+    }
+    template <typename T>
+    void val(T v) { bytes(&v, sizeof(v)); }
+};
+
+uint64_t snapshot_tag(const VnEnv *e, const RoomTables &rt) {
+    const EnvLayout &l = e->lay;
+    Fnv f;
+    f.val<int32_t>(VN_ABI_VERSION);
+    f.val<int32_t>(l.variant);
+    f.val<int32_t>(e->N);
+    f.val<int32_t>(e->cfg.local_map_length);
+    for (const int32_t v : {l.obs_dim, l.pw, l.pd, l.ph, l.nbx, l.nby, l.nwx, l.nwy, l.sbits, l.sline, l.defer, l.pcache})
+        f.val<int32_t>(v);
+    for (const uint32_t v : {l.map_bytes, l.agent_bytes, l.plane_bytes, l.xp_off, l.yp_off, l.sy_off, l.sz_off, l.qz_off})
+        f.val<uint32_t>(v);
+    f.val<int32_t>(e->tuning.pcache_cap);
+    f.val<int32_t>(e->tuning.defer);
+    f.val<int32_t>(e->tuning.simple_layout);
+    f.val<int32_t>(e->cfg.use_room_draw);
+    f.val<int32_t>(e->cfg.autoreset);
+    f.val<double>(e->cfg.crash_penalty);
+    f.val<double>(e->cfg.finish_percentage);
+    f.val<int64_t>(e->cfg.agent_id_base);
+    f.val<int64_t>(e->cfg.seed_stride);
+    f.bytes(rt.desc.data(), rt.desc.size() * sizeof(uint32_t));
+    f.bytes(rt.rays.data(), rt.rays.size() * sizeof(RayRec));
+    f.bytes(rt.starts.data(), rt.starts.size() * sizeof(uint32_t));
+    return f.h;
+}
+
 }  // namespace
 
 std::atomic<int32_t> vn_detail::g_options[vn_detail::N_OPTIONS] = {{0}, {1}, {1}, {0}};
@@ -360,6 +423,7 @@ int vn_create_tuned(const VnRoomSet *rooms, int32_t n_agents, const VnConfig *cf
     const size_t belief_bytes = (size_t)e->lay.agent_bytes * (size_t)n_agents;
     if (const int rc = alloc_buffers(e.get(), rt, belief_bytes + belief_off, belief_contig)) return rc;
     e->params = env_params(e.get(), belief_off);
+    e->snap_tag = snapshot_tag(e.get(), rt);
     if (const hipError_t he = upload(e.get(), *rooms, rt, lut))
         return fail(VN_ERR_HIP, "vn_create upload: %s", hipGetErrorString(he));
     *out = e.release();
@@ -462,6 +526,70 @@ int vn_export_belief(VnEnv *env, int8_t *belief_out, void *stream) {
     if (env->lay.variant == VN_VARIANT_SIMPLE)
         return vn_simple::export_belief(&p, belief_out, env->lay.pw, env->lay.pd, (hipStream_t)stream);
     return vn_cubic::export_belief(&p, belief_out, env->lay.pw, env->lay.pd, (hipStream_t)stream);
+}
+
+int vn_import_state(VnEnv *env, const int64_t *state, const int8_t *belief, const uint8_t *mask, float *obs,
+                    int32_t *n_rejected, void *stream) {
+    if (!env || !state || !belief) return fail(VN_ERR_INVALID, "NULL argument");
+    if (env->lay.variant == VN_VARIANT_SIMPLE)
+        return fail(VN_ERR_INVALID, "vn_import_state: the simpleEnv variant has no portable import (its dense map "
+                                    "does not determine the device state); use vn_snapshot_save / vn_snapshot_load");
+    DeviceGuard dg(env->device);
+    const Params p = call_params(env);
+    // an imported agent's window record is stale (its hot word says so); the
+    // other agents' records stay valid and are loaded after the state
+    env->wrec_written = false;
+    return vn_state::import_state(&p, state, belief, mask, obs, n_rejected, env->lay.pw, env->lay.pd,
+                                  (hipStream_t)stream);
+}
+
+int vn_snapshot_tag(const VnEnv *env, uint64_t *tag) {
+    if (!env || !tag) return fail(VN_ERR_INVALID, "NULL argument");
+    *tag = env->snap_tag;
+    return VN_OK;
+}
+
+int vn_snapshot_bytes(const VnEnv *env, int64_t *bytes) {
+    if (!env || !bytes) return fail(VN_ERR_INVALID, "NULL argument");
+    SnapPart parts[6];
+    const int n = snap_parts(env, parts);
+    size_t total = 0;
+    for (int k = 0; k < n; ++k) total += (parts[k].bytes + SNAP_ALIGN - 1) & ~(SNAP_ALIGN - 1);
+    *bytes = (int64_t)total;
+    return VN_OK;
+}
+
+int vn_snapshot_save(VnEnv *env, void *dst, void *stream) {
+    if (!env || !dst) return fail(VN_ERR_INVALID, "NULL argument");
+    DeviceGuard dg(env->device);
+    SnapPart parts[6];
+    const int n = snap_parts(env, parts);
+    char *d = static_cast<char *>(dst);
+    for (int k = 0; k < n; ++k) {
+        VN_HIP(hipMemcpyAsync(d, parts[k].ptr, parts[k].bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        d += (parts[k].bytes + SNAP_ALIGN - 1) & ~(SNAP_ALIGN - 1);
+    }
+    return VN_OK;
+}
+
+int vn_snapshot_load(VnEnv *env, const void *src, uint64_t tag, void *stream) {
+    if (!env || !src) return fail(VN_ERR_INVALID, "NULL argument");
+    if (tag != env->snap_tag)
+        return fail(VN_ERR_INVALID, "vn_snapshot_load: the snapshot's tag %016llx is not this env's (%016llx): "
+                                    "another variant, size, layout, tuning, config or room set",
+                    (unsigned long long)tag, (unsigned long long)env->snap_tag);
+    DeviceGuard dg(env->device);
+    SnapPart parts[6];
+    const int n = snap_parts(env, parts);
+    const char *s = static_cast<const char *>(src);
+    for (int k = 0; k < n; ++k) {
+        VN_HIP(hipMemcpyAsync(parts[k].ptr, s, parts[k].bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        s += (parts[k].bytes + SNAP_ALIGN - 1) & ~(SNAP_ALIGN - 1);
+    }
+    // the copied hot words carry their window-record bits and the records came
+    // with them, so the next launch reads each record after its state
+    env->wrec_written = false;
+    return VN_OK;
 }
 
 #ifdef VN_DIAG

@@ -15,6 +15,7 @@ include/voxnav.h.  Public API:
   PPOLearner          (Recurrent)PPO.train on the collector's device buffers (+ DDP)
   evaluate_policy     evaluate_grid.py's deterministic-episode metrics, batched
   save_checkpoint / load_checkpoint   SB3 .zip layout, Grid_Train naming
+  checkpoint.save_env_state / load_env_state   an env's agents (.npz: portable exports or a raw snapshot)
   sharding            multi-GPU agent sharding helpers
 """
 from . import rooms  # noqa: F401

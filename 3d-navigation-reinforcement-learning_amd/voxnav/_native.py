@@ -84,6 +84,11 @@ _SIGS = {
     "vn_export_state": (C.c_int, [P, P, P]),
     "vn_kernel_label": (C.c_int, [P, C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_int32]),
     "vn_export_belief": (C.c_int, [P, P, P]),
+    "vn_import_state": (C.c_int, [P, P, P, P, P, P, P]),
+    "vn_snapshot_tag": (C.c_int, [P, C.POINTER(C.c_uint64)]),
+    "vn_snapshot_bytes": (C.c_int, [P, C.POINTER(C.c_int64)]),
+    "vn_snapshot_save": (C.c_int, [P, P, P]),
+    "vn_snapshot_load": (C.c_int, [P, P, C.c_uint64, P]),
     "vn_gae": (C.c_int, [P, P, P, P, P, C.c_int32, C.c_int32, C.c_double, C.c_double, P, P, P]),
     "vn_lstm_cell": (C.c_int, [P, C.c_int64, P, P, P, P, P, P, P, C.c_int32, C.c_int32, C.c_int32, P]),
     "vn_policy_head": (C.c_int, [P, P, C.c_int32, C.c_int32, P, P, C.c_int32, P, P, C.c_uint64, C.c_uint64,

@@ -30,11 +30,13 @@ import zipfile
 from pathlib import Path
 from typing import Dict, Optional, Tuple, Union
 
+import numpy as np
 import torch
 
 from .policy import ActorCriticPolicy, RecurrentActorCriticPolicy
 
 FORMAT_VERSION = "voxnav-sb3-layout-1"
+ENV_STATE_VERSION = 1      # save_env_state's .npz (both forms)
 
 
 def arch_str(net_arch: Dict[str, list]) -> str:
@@ -207,3 +209,56 @@ def load_optimizer_state(path: Union[str, Path], optimizer: torch.optim.Optimize
             if s and "step" in s and torch.is_tensor(s["step"]):
                 s["step"] = s["step"].to(device=prm.device, dtype=torch.float32)
     return True
+
+
+# ------------------------------------------------------------------ env state
+# One .npz per env, next to (not inside) the policy checkpoint, in one of two
+# forms, each with ``format_version``, ``form`` and ``t`` (the env's
+# random-policy step counter):
+#   "portable" (CubicEnv only): ``state`` int64 [N, 16] and ``belief`` int8
+#       [N, pad_w, pad_d, pad_h], the exports -- loadable into an env of any
+#       belief layout or shard size with the same rooms (import_state);
+#   "raw": ``blob`` uint8 and ``tag`` uint64, a whole-env snapshot -- loadable
+#       only into an env built alike (restore), the one form of the simpleEnv
+#       variant.
+# A collector's or learner's mid-rollout state (LSTM state, rollout buffers,
+# Monitor counters) is not part of either.
+def save_env_state(path: Union[str, Path], env, raw: Optional[bool] = None) -> Path:
+    """Write ``env``'s state to ``path`` (.npz).  ``raw=None`` picks the
+    portable form for the CubicEnv variant and the raw form for simpleEnv."""
+    path = Path(path)
+    if path.suffix != ".npz":
+        path = path.with_suffix(".npz")
+    if raw is None:
+        raw = int(env.variant) != 0
+    if not raw and int(env.variant) != 0:
+        raise ValueError("the portable form is for the CubicEnv variant only (simpleEnv: raw=True)")
+    path.parent.mkdir(parents=True, exist_ok=True)
+    head = dict(format_version=np.int64(ENV_STATE_VERSION), t=np.int64(env._t))
+    if raw:
+        snap = env.snapshot()
+        np.savez_compressed(path, form=np.str_("raw"), blob=snap.data.cpu().numpy(),
+                            tag=np.uint64(snap.tag), **head)
+    else:
+        np.savez_compressed(path, form=np.str_("portable"), state=env.export_state().cpu().numpy(),
+                            belief=env.belief().cpu().numpy(), **head)
+    return path
+
+
+def load_env_state(path: Union[str, Path], env) -> None:
+    """Put the state saved by ``save_env_state`` into ``env``: a portable
+    file through ``import_state`` (all agents, validated), a raw one through
+    ``restore`` (refused unless the env is built like the one that saved it)."""
+    from .env import EnvSnapshot
+    with np.load(path, allow_pickle=False) as z:
+        if "format_version" not in z.files or int(z["format_version"]) != ENV_STATE_VERSION:
+            got = int(z["format_version"]) if "format_version" in z.files else None
+            raise ValueError(f"{path}: env state format version {got!r}, this build reads {ENV_STATE_VERSION}")
+        form, t = str(z["form"]), int(z["t"])
+        if form == "portable":
+            env.import_state(torch.from_numpy(z["state"]), torch.from_numpy(z["belief"]))
+            env._t = t
+        elif form == "raw":
+            env.restore(EnvSnapshot(int(z["tag"]), torch.from_numpy(z["blob"]), t))
+        else:
+            raise ValueError(f"{path}: unknown env state form {form!r}")

@@ -48,6 +48,14 @@ class Rollout(NamedTuple):
     actions: Optional[torch.Tensor]  # i32 [K, N]
 
 
+class EnvSnapshot(NamedTuple):
+    """A whole-env raw snapshot (``BatchedGridEnv.snapshot``): opaque,
+    layout-native bytes that only an env with the same tag can load."""
+    tag: int                     # vn_snapshot_tag of the env that took it
+    data: torch.Tensor           # uint8 [vn_snapshot_bytes], on the env's device
+    t: int                       # the env's random-policy step counter
+
+
 def _variant_code(v) -> int:
     if isinstance(v, str):
         try:
@@ -91,6 +99,11 @@ class BatchedGridEnv:
             raise _native.VoxnavError("BatchedGridEnv needs a ROCm GPU (torch.cuda.is_available() is False)")
         self.lib = lib if lib is not None else _native.load()
         self.room_set = as_room_set(rooms, room_path, width, depth, height)
+        # what clone() builds its env from (the parsed rooms stand in for room_path / width, depth, height)
+        self._ctor = dict(num_agents=num_agents, rooms=self.room_set, local_map_length=local_map_length,
+                          crash_penalty=crash_penalty, autoreset=autoreset, device=device, agent_id_base=agent_id_base,
+                          seed_stride=seed_stride, finish_percentage=finish_percentage, variant=variant, lib=lib,
+                          tuning=None if tuning is None else dict(tuning))
         self.num_agents = int(num_agents)
         self.local_map_length = int(local_map_length)
         if not 1 <= self.local_map_length <= _native.VN_MAX_L:
@@ -131,6 +144,7 @@ class BatchedGridEnv:
                                            dtype=np.int64)
         self._was_reset = False
         self._t = 0   # global step counter for the random policy stream
+        self.last_rejected = None   # device i32 [1]: agents the last import_state rejected
 
     # ------------------------------------------------------------------ utils
     def close(self):
@@ -332,3 +346,81 @@ class BatchedGridEnv:
         out = torch.empty((self.num_agents, i.pad_w, i.pad_d, i.pad_h), dtype=torch.int8, device=self.device)
         _native.check(self.lib.vn_export_belief(self._h, _ptr(out), self._stream()), "vn_export_belief")
         return out
+
+    # ------------------------------------------------- state import, snapshots
+    def import_state(self, state: torch.Tensor, belief: torch.Tensor, mask: Optional[torch.Tensor] = None,
+                     out: Optional[torch.Tensor] = None, check: bool = True) -> torch.Tensor:
+        """The exports' other direction (CubicEnv variant; ``vn_import_state``):
+        agent i takes the attributes of ``state[i]`` (``export_state``'s 16
+        int64 fields) and the map ``belief[i]`` (``belief()``'s int8
+        encoding), for the agents with ``mask[i]`` (None: all), in whatever
+        belief layout this env has.  Returns obs f32 [N, 80]: ``get_obs()``
+        of the imported agents (rows of the others as in ``out`` / zero).
+        Agents the device-side validation rejects are left untouched;
+        ``check=True`` reads their count back and raises ``VoxnavError``
+        naming it."""
+        N, i = self.num_agents, self.info
+        st = torch.as_tensor(state).to(device=self.device, dtype=torch.int64).contiguous()
+        bl = torch.as_tensor(belief).to(device=self.device, dtype=torch.int8).contiguous()
+        if tuple(st.shape) != (N, _native.VN_STATE_FIELDS):
+            raise ValueError(f"state: expected [{N}, {_native.VN_STATE_FIELDS}], got {tuple(st.shape)}")
+        if tuple(bl.shape) != (N, i.pad_w, i.pad_d, i.pad_h):
+            raise ValueError(f"belief: expected {(N, i.pad_w, i.pad_d, i.pad_h)}, got {tuple(bl.shape)}")
+        m = None
+        if mask is not None:
+            m = torch.as_tensor(mask).to(device=self.device, dtype=torch.uint8).reshape(N).contiguous()
+            if not self._was_reset:
+                raise ValueError("a partial import needs an env that was reset (or fully imported) before")
+        if out is None:
+            out = torch.zeros((N, self.obs_dim), dtype=torch.float32, device=self.device)
+        elif (out.dtype != torch.float32 or tuple(out.shape) != (N, self.obs_dim) or not out.is_contiguous()
+              or out.device != self.device):
+            raise ValueError(f"out: expected contiguous float32 {(N, self.obs_dim)} on {self.device}")
+        rej = torch.zeros(1, dtype=torch.int32, device=self.device)
+        _native.check(self.lib.vn_import_state(self._h, _ptr(st), _ptr(bl), _ptr(m), _ptr(out), _ptr(rej),
+                                               self._stream()), "vn_import_state")
+        self.last_rejected = rej          # device i32 [1]: what check=False callers may read later
+        if check:
+            n = int(rej.item())
+            if n:
+                raise _native.VoxnavError(f"vn_import_state rejected {n} of {N} agents (left untouched)")
+        if m is None:
+            self._was_reset = True
+        return out
+
+    def _snapshot_tag(self) -> int:
+        tag = C.c_uint64()
+        _native.check(self.lib.vn_snapshot_tag(self._h, C.byref(tag)), "vn_snapshot_tag")
+        return int(tag.value)
+
+    def snapshot(self) -> EnvSnapshot:
+        """A raw copy of every mutable per-agent buffer (both variants, every
+        layout), taken on the current stream."""
+        n = C.c_int64()
+        _native.check(self.lib.vn_snapshot_bytes(self._h, C.byref(n)), "vn_snapshot_bytes")
+        data = torch.empty(int(n.value), dtype=torch.uint8, device=self.device)
+        _native.check(self.lib.vn_snapshot_save(self._h, _ptr(data), self._stream()), "vn_snapshot_save")
+        return EnvSnapshot(self._snapshot_tag(), data, int(self._t))
+
+    def restore(self, snap: EnvSnapshot) -> None:
+        """Load a snapshot taken from this env or from one built alike (same
+        variant, agents, rooms, config and creation-time tuning); any other
+        raises ``VoxnavError`` and leaves this env as it was."""
+        data = snap.data.to(device=self.device, dtype=torch.uint8).contiguous()
+        n = C.c_int64()
+        _native.check(self.lib.vn_snapshot_bytes(self._h, C.byref(n)), "vn_snapshot_bytes")
+        if int(snap.tag) == self._snapshot_tag() and data.numel() != int(n.value):
+            raise ValueError(f"snapshot holds {data.numel()} bytes, this env's snapshots have {int(n.value)}")
+        _native.check(self.lib.vn_snapshot_load(self._h, _ptr(data), int(snap.tag), self._stream()),
+                      "vn_snapshot_load")
+        self._t = int(snap.t)
+        self._was_reset = True
+
+    def clone(self) -> "BatchedGridEnv":
+        """A new env built from the same arguments, in this env's state."""
+        other = BatchedGridEnv(**self._ctor)
+        if self._tuning is not None:      # launch-time fields changed by set_tuning
+            other.set_tuning(**{f: getattr(self._tuning, f) for f in ("prio", "dflush", "wrec_k", "wrec_early")})
+        if self._was_reset:
+            other.restore(self.snapshot())
+        return other

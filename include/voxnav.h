@@ -212,6 +212,77 @@ int vn_export_state(VnEnv *env, int64_t *state_out, void *stream);
 int vn_export_belief(VnEnv *env, int8_t *belief_out, void *stream);
 
 /*
+ * The exports' other direction (CubicEnv variant): every agent with
+ * mask[i] != 0 (mask NULL = all) takes the reference attributes of its state
+ * row (vn_export_state's field order; field 14, max_steps, is derived and
+ * ignored; field 15 is the next auto-reset seed) and the internal_grid of its
+ * belief row (vn_export_belief's encoding; a count above 63 is clamped to 63,
+ * as the device map saturates; cells outside the agent's room are ignored),
+ * and its obs row (device f32 [N][80], may be NULL) receives get_obs() of
+ * that agent -- with get_obs's own side effects (envs/CubicEnv.py:254-312,
+ * :345-397): the six sensing rays from the agent's cell mark what they see,
+ * near_wall is set if a wall is one cell away, cells_insight_down is
+ * recomputed.  For a state taken from the exports all of that is the
+ * identity.  (The row is get_obs() of the state the last step LEFT: step()
+ * takes its own observation before it updates last_action, last_bump and
+ * was_near_wall, :120-124, so obs[68..70] of the row that step returned show
+ * the values of before the step, which no export holds; the other 77 floats
+ * are that row's.)  Afterwards the agent is indistinguishable from one that reached
+ * this state by stepping, in whatever belief layout this env was planned with
+ * (VnTuning), whichever layout the exporting env had: obs, f64 rewards,
+ * flags, exports and the auto-reset seed schedule continue bit for bit.
+ * Unmasked agents keep their state, map and obs row.  Stream-ordered; the
+ * host is not synchronised.
+ *
+ * Validation runs on the device before anything of the agent is written.  A
+ * rejected agent is left untouched (its obs row too) and counted in
+ * *n_rejected (device i32 [1], may be NULL; zeroed by the call first):
+ *   room outside the env's rooms; position outside that room or on a wall
+ *   cell; facing not 0..3; last_action not 0..5; a flag not 0/1;
+ *   cells_insight_down not 0..L; seed outside [0, 2^32); a negative counter,
+ *   or a visited_count above the room's cell count; inside the room a value
+ *   below -2, -2 where the room has no wall or a value >= 0 where it has one;
+ *   the agent's own cell below 1.
+ * A step_count above the hot state's 24-bit field (16777215) or a bump_count
+ * above its 26-bit field (67108863) is CLAMPED to that maximum, not rejected:
+ * the device counters saturate there, so this is the value stepping would
+ * have reached.
+ * VN_ERR_INVALID (host, nothing launched): NULL env / state / belief, or an
+ * env of the simpleEnv variant.
+ *
+ * Out of scope: a portable import for the simpleEnv variant (its dense map
+ * does not determine the device state: a cell the agent stood on that the
+ * edge quirk later turned into 2 exports like a quirk-only cell, while
+ * knownness is derived from the stood set) -- vn_snapshot_* covers that
+ * variant; a collector's or learner's mid-rollout state (LSTM state, rollout
+ * buffers, Monitor counters); setters on the GridAgent facade.
+ */
+int vn_import_state(VnEnv *env, const int64_t *state, const int8_t *belief, const uint8_t *mask, float *obs,
+                    int32_t *n_rejected, void *stream);
+
+/*
+ * Whole-env raw snapshots (both variants, every layout): an opaque,
+ * layout-native copy of every mutable per-agent buffer -- the hot state with
+ * the window records behind it, the next seeds, the belief blocks, the
+ * goals, the simpleEnv draw-ahead, the stood rows and masks -- as
+ * stream-ordered device-to-device copies into / from one caller-owned device
+ * blob of vn_snapshot_bytes bytes.  The blob has no header: no call reads
+ * device memory back.  What its bytes mean is named by vn_snapshot_tag, a
+ * host-side hash of the ABI version, variant, N, L, the planned layout, the
+ * creation-time tuning, the config and the room tables; vn_snapshot_load
+ * returns VN_ERR_INVALID when `tag` is not the env's own and then touches
+ * nothing.  After a load (as after an import) the env's "the previous launch
+ * wrote every window record" flag is false: the copied hot words keep their
+ * record bits and the records were copied with them, so the next launch
+ * reads each agent's record after its state instead of beside it -- the
+ * records are consumed, the bit is not cleared.  No reference counterpart.
+ */
+int vn_snapshot_tag(const VnEnv *env, uint64_t *tag);
+int vn_snapshot_bytes(const VnEnv *env, int64_t *bytes);
+int vn_snapshot_save(VnEnv *env, void *dst, void *stream);
+int vn_snapshot_load(VnEnv *env, const void *src, uint64_t tag, void *stream);
+
+/*
  * GAE advantage/return scan (SB3 RolloutBuffer.compute_returns_and_advantage,
  * called from RecurrentPPO.learn at train/Grid_Train.py:228).  All arrays
  * device f32, [T][N]-major; last_values/dones [N].
