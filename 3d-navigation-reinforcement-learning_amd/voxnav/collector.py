@@ -61,6 +61,10 @@ from .monitor import EpisodeMonitor
 from .policy import ActorCriticPolicy, RecurrentActorCriticPolicy
 
 
+MAX_ACTIONS = 8      # HEAD_MAX_A (csrc/voxnav_collect.hip), vn_mlp_head_f32's n_actions bound
+MAX_LATENT = 4096    # vn_policy_head's P bound (include/voxnav.h)
+
+
 def _p(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
@@ -100,6 +104,16 @@ class _Weights:
         g = lambda t: t.detach().to(device=device, dtype=dtype).contiguous()  # noqa: E731
         self.dtype = dtype
         self.recurrent = bool(getattr(policy, "recurrent", False))
+        # every head kernel (vn_policy_head[_bf16], vn_mlp_head_f32) takes at most
+        # MAX_ACTIONS actions and a latent width % 4 up to MAX_LATENT: refused
+        # here rather than by the first step's launch
+        n_act, lat = policy.action_net.weight.shape
+        if n_act > MAX_ACTIONS:
+            raise ValueError(f"the collector's head kernels take at most {MAX_ACTIONS} actions (policy has {n_act})")
+        if lat % 4 or not 4 <= lat <= MAX_LATENT:
+            raise ValueError(f"the collector's head kernels take a latent width % 4 == 0 in 4..{MAX_LATENT} "
+                             f"(policy has {lat})")
+        self.fused = False
         if self.recurrent:
             la, lc = policy.lstm_actor, policy.lstm_critic
             if la.num_layers != 1 or lc.num_layers != 1:
@@ -150,11 +164,12 @@ class _Weights:
         if self.wv.shape[0] != self.P:
             raise NotImplementedError("pi and vf latents must have the same width")
         # the MLPs and heads in one launch (vn_mlp_head_f32): layer widths 128 / 256,
-        # at most 4 layers, inputs % 16 <= 256, at most 8 actions; W^T per layer.
+        # at most 4 layers, inputs % 16 <= 256 (at most 8 actions: checked above);
+        # W^T per layer.
         # VOXNAV_MLP_HEAD=0: the per-layer kernels + vn_policy_head (A/B knob)
         k0 = self.pi[0][0].shape[1] if self.pi else 0
         self.mlp_head = (self.f32mlp and 1 <= len(self.pi) <= 4 and all(w.shape[0] in (128, 256) for w, _ in self.pi)
-                         and k0 % 16 == 0 and 16 <= k0 <= 256 and self.P == widths[-1] and self.A <= 8
+                         and k0 % 16 == 0 and 16 <= k0 <= 256 and self.P == widths[-1]
                          and os.environ.get("VOXNAV_MLP_HEAD", "1") != "0")
         if self.mlp_head:
             self.widths = widths

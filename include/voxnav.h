@@ -329,7 +329,8 @@ int vn_get_option(int32_t option, int32_t *value);
  *   gh       [n_lstm][N][4H] (h @ W_hh^T) or NULL when the state is zero
  *   b_ih, b_hh [n_lstm][4H];  h (out), c (in/out) [n_lstm][N][H]
  *   h_store, c_store  [n_lstm][N][H] copies for the rollout buffer, or NULL
- * H must be a multiple of 4.
+ * H must be a multiple of 4; gx_row_stride a multiple of 4, at least
+ * n_lstm * 4H (a row may carry padding after its gates).
  */
 int vn_lstm_cell(const float *gx, int64_t gx_row_stride, const float *gh, const float *b_ih, const float *b_hh,
                  float *h, float *c, float *h_store, float *c_store, int32_t n_lstm, int32_t N, int32_t H,
@@ -438,7 +439,10 @@ int vn_linear_f32(int32_t n_branch, const float *const *x, int64_t ldx, const fl
  *   actions (i32 [N]): Philox4x32-10(key=sample_seed, ctr=(agent_id_base+n,
  *   t | 2^63)) word 0 -> u = (w >> 8) / 2^24, first a with u < cdf[a]
  *   (argmax of the logits when deterministic); log_probs = logit - logsumexp.
- * n_actions <= 8, P a multiple of 4.
+ * 1 <= n_actions <= 8 (0 with latent_pi NULL); P a multiple of 4 in
+ * 4..4096.  A block keeps the head weights in (n_actions + 1) * P * 4 bytes
+ * of dynamic LDS: 147,456 B at the bounds (8 actions, P = 4096), within the
+ * CU's 160 KiB.  Anything else returns VN_ERR_INVALID without a launch.
  */
 int vn_policy_head(const float *latent_pi, const float *latent_vf, int32_t N, int32_t P, const float *w_action,
                    const float *b_action, int32_t n_actions, const float *w_value, const float *b_value,

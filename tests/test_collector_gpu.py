@@ -16,11 +16,35 @@ and up to 6 % of the draws may flip within 0.08 of a CDF boundary.  The
 GAE kernel is bit-exact against the f32 oracle on the GPU's own
 rewards/values.  The kernels alone are compared with the plain-PyTorch f32
 policy (voxnav.policy.forward_torch) at 2e-5.
+
+One collector case runs per row of helpers.COLLECTOR_PATHS (INTEGRATION.md,
+"Collector paths"), each asserting first that its policy is dispatched to
+the kernels the row names.  Maximum |gpu - f64| measured on an MI355X on the
+boxes rooms (64 agents, T = 96 x 2 rollouts, MLP policies T = 80), against
+the bounds above -- the library-GEMM paths (P2 - P4: torch.mm / addmm in f32,
+sums of at most 464 terms) sit as far inside the f32 bounds as the
+matrix-core kernels:
+
+  path                                      values   log-probs  h / c     adv / returns
+  P1 fused LSTM + vn_linear + policy_head   3.3e-7   5.3e-7     1.6e-7    4.3e-6
+  P2 mm + lstm_cell + addmm + policy_head   1.5e-7   4.5e-7     1.1e-7    5.3e-6
+  P3 mm + lstm_cell + mlp_head (K0 = 48)    3.0e-7   4.5e-7     1.3e-7    4.8e-6
+  P4 addmm + policy_head (MLP policy)       2.1e-7   4.3e-7     --        4.2e-6
+  P5 vn_linear + policy_head (MLP policy)   4.1e-7   5.0e-7     --        4.4e-6
+  P6 bf16: mm + lstm_cell_bf16 + head_bf16  2.6e-3   2.9e-3     1.7e-3    2.8e-3
+  (bootstrapped rewards: 4.8e-7 on every f32 path, 1.6e-3 on P6; no f32 draw
+  differed from the float64 draw)
+
+One step against forward_torch (test_kernels_match_torch_fp32, bound 2e-5):
+values / log-probs / h / c at most 6.6e-7 / 9.5e-7 / 2.4e-7 / 4.4e-7 over
+P0 - P3.  act() without stored states (store_lstm_states=False, P0 and P2,
+f32 bounds): at most 5.2e-7 / 6.3e-7 / 2.2e-7 / 4.6e-7.
 """
 import numpy as np
 import pytest
 
-from helpers import box_text
+from helpers import COLLECTOR_PATHS, box_text, path_flags, path_policy
+from helpers import philox_uniform as _philox_u
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -49,14 +73,30 @@ def _rooms():
 def _close(a, b, atol, rtol, what):
     a = np.asarray(a, np.float64)
     b = np.asarray(b, np.float64)
-    bad = np.abs(a - b) > atol + rtol * np.abs(b)
+    bound = atol + rtol * np.abs(b)
+    bad = np.abs(a - b) > bound
+    # the figures behind the module docstring's "measured" table (shown with pytest -s)
+    print(f"{what}: max err {np.abs(a - b).max():.3g}, {(np.abs(a - b) / bound).max():.3f} of the bound")
     assert not bad.any(), f"{what}: {bad.sum()} of {bad.size} out of tolerance, max err {np.abs(a - b).max():.3g}"
 
 
-def _policy(kind):
+# the default-architecture policies of _policy(kind) as rows of helpers.COLLECTOR_PATHS
+DEFAULT_PATH = {("lstm", "f32"): "P0", ("lstm", "bf16"): "P7", ("mlp", "f32"): "M0", ("mlp", "bf16"): "M1"}
+
+
+def _assert_path(col, pid):
+    """The collector runs the kernels the table promises for this policy."""
+    assert path_flags(col.w) == COLLECTOR_PATHS[pid][3], f"{pid} is dispatched to another path"
+
+
+def _policy(kind, pid=None):
     from voxnav.policy import ActorCriticPolicy, RecurrentActorCriticPolicy
     torch.manual_seed(7)
-    pol = RecurrentActorCriticPolicy() if kind == "lstm" else ActorCriticPolicy()
+    if pid is not None:
+        assert (COLLECTOR_PATHS[pid][0] is not None) == (kind == "lstm")
+        pol = path_policy(pid)
+    else:
+        pol = RecurrentActorCriticPolicy() if kind == "lstm" else ActorCriticPolicy()
     # larger head weights than SB3's 0.01 init so the draws are not ~uniform
     with torch.no_grad():
         pol.action_net.weight.mul_(100.0)
@@ -76,39 +116,48 @@ def _set_rooms(name):
 C5_SHARD = (7 * 65536, 8 * 65536)
 
 COLLECT_CASES = [
-    # (policy, T, rollouts, dtype, rooms, L, N, (agent_id_base, seed_stride) or None)
+    # (policy, T, rollouts, dtype, rooms, L, N, (agent_id_base, seed_stride) or None, path id or None)
     # T=96 / 80 > 4 x 18 (the smallest box's free cells): the bootstrap stash
     # is flushed once inside the rollout (collector._flush_every = 72)
-    ("lstm", 96, 2, "f32", "boxes", 4, 64, None), ("mlp", 80, 1, "f32", "boxes", 4, 64, None),
-    ("lstm", 48, 2, "bf16", "boxes", 4, 64, None), ("mlp", 48, 1, "bf16", "boxes", 4, 64, None),
+    ("lstm", 96, 2, "f32", "boxes", 4, 64, None, None), ("mlp", 80, 1, "f32", "boxes", 4, 64, None, None),
+    ("lstm", 48, 2, "bf16", "boxes", 4, 64, None, None), ("mlp", 48, 1, "bf16", "boxes", 4, 64, None, None),
     # BASELINE configs at the reference's settings, a few hundred agents:
     # C4 = PPO-LSTM on P3_training (L=10, n_steps 128), C3 = PPO-MLP on P2_training
-    ("lstm", 128, 2, "f32", "P3_training", 10, 192, None), ("mlp", 128, 3, "f32", "P2_training", 10, 256, None),
+    ("lstm", 128, 2, "f32", "P3_training", 10, 192, None, None),
+    ("mlp", 128, 3, "f32", "P2_training", 10, 256, None, None),
     # C4 through the bf16 policy path the bench also reports (its stated bounds)
-    ("lstm", 128, 2, "bf16", "P3_training", 10, 192, None),
+    ("lstm", 128, 2, "bf16", "P3_training", 10, 192, None, None),
     # C5: the last shard's collector -- Philox draws keyed by global id, seeds
     # on the 524,288 stride (the bench's N>1 path)
-    ("lstm", 128, 2, "f32", "P3_training", 10, 192, C5_SHARD),
+    ("lstm", 128, 2, "f32", "P3_training", 10, 192, C5_SHARD, None),
+    # every other row of helpers.COLLECTOR_PATHS (the shapes the reference's policy
+    # does not take): the recurrent ones over two rollouts (the carried state)
+    ("lstm", 96, 2, "f32", "boxes", 4, 64, None, "P1"), ("lstm", 96, 2, "f32", "boxes", 4, 64, None, "P2"),
+    ("lstm", 96, 2, "f32", "boxes", 4, 64, None, "P3"), ("mlp", 80, 1, "f32", "boxes", 4, 64, None, "P4"),
+    ("mlp", 80, 1, "f32", "boxes", 4, 64, None, "P5"), ("lstm", 96, 2, "bf16", "boxes", 4, 64, None, "P6"),
 ]
 
 
 def _case_id(c):
-    return f"{c[0]}-{c[3]}-{c[4]}-T{c[1]}" + ("-C5shard" if c[7] else "")
+    return f"{c[0]}-{c[3]}-{c[4]}-T{c[1]}" + ("-C5shard" if c[7] else "") + (f"-{c[8]}" if c[8] else "")
 
 
-@pytest.mark.parametrize("kind,T,rollouts,dtype,rooms,L,N,shard", COLLECT_CASES, ids=[_case_id(c) for c in COLLECT_CASES])
-def test_collector_matches_oracle(voxnav, kind, T, rollouts, dtype, rooms, L, N, shard):
+@pytest.mark.parametrize("kind,T,rollouts,dtype,rooms,L,N,shard,pid", COLLECT_CASES,
+                         ids=[_case_id(c) for c in COLLECT_CASES])
+def test_collector_matches_oracle(voxnav, kind, T, rollouts, dtype, rooms, L, N, shard, pid):
     from oracle import collector_oracle as co
     from oracle.oracle import OracleEnv, gae as gae32
     from voxnav.collector import RolloutCollector
     from voxnav.env import BatchedGridEnv
     from voxnav.policy import numpy_weights
     prod, orooms = _rooms() if rooms == "boxes" else _set_rooms(rooms)
-    pol = _policy(kind)
+    pol = _policy(kind, pid)
     gid_base, stride = shard if shard else (0, N)
     env = BatchedGridEnv(num_agents=N, rooms=prod, local_map_length=L, device="cuda:0", agent_id_base=gid_base,
                          seed_stride=stride)
     col = RolloutCollector(env, pol.to("cuda:0"), n_steps=T, sample_seed=1234, reset_seed=42, policy_dtype=dtype)
+    _assert_path(col, pid or DEFAULT_PATH[kind, dtype])
+    assert COLLECTOR_PATHS[pid or DEFAULT_PATH[kind, dtype]][2] == dtype
     # f32: the reference's dtype, tight bounds; bf16 GEMM operands (8-bit
     # mantissa): looser bounds and some draws flip near a CDF boundary
     tol = dict(v=(1e-4, 1e-4), r=(1e-4, 1e-5), adv=(2e-3, 1e-4), flip=1e-5, nflip=2) if dtype == "f32" else \
@@ -181,19 +230,30 @@ def test_collector_matches_oracle(voxnav, kind, T, rollouts, dtype, rooms, L, N,
     assert total_boot > 0, "the test rooms must produce truncations inside the rollout"
 
 
-def test_kernels_match_torch_fp32(voxnav):
-    """vn_lstm_cell + vn_policy_head (through the collector's forward) vs nn.LSTM/nn.Linear."""
+@pytest.mark.parametrize("pid", ["P0", "P1", "P2", "P3"])
+def test_kernels_match_torch_fp32(voxnav, pid):
+    """One collector step on each f32 LSTM path (through the collector's
+    forward) vs nn.LSTM / nn.Linear in plain PyTorch f32:
+      P0  vn_lstm_fused_f32 + vn_mlp_head_f32
+      P1  vn_lstm_fused_f32 + vn_linear_f32 per layer + vn_policy_head
+      P2  torch.mm + vn_lstm_cell[_masked] + addmm + vn_policy_head
+      P3  torch.mm + vn_lstm_cell[_masked] + vn_mlp_head_f32 (K0 = 48)
+    the plain step at 2e-5, arg-max in deterministic mode, and the rollout
+    entry (unmasked state + episode_starts) bitwise the plain step on the
+    masked state."""
     from voxnav.collector import RolloutCollector
     from voxnav.env import BatchedGridEnv
     N = 300
+    H = COLLECTOR_PATHS[pid][0]
     prod, _ = _rooms()
-    pol = _policy("lstm").to("cuda:0")
+    pol = _policy("lstm", None if pid == "P0" else pid).to("cuda:0")
     env = BatchedGridEnv(num_agents=N, rooms=prod, local_map_length=4, device="cuda:0")
     col = RolloutCollector(env, pol, n_steps=4)
+    _assert_path(col, pid)
     g = torch.Generator(device="cuda:0").manual_seed(5)
     obs = torch.rand((N, 80), device="cuda:0", generator=g)
-    h = torch.randn((2, N, 256), device="cuda:0", generator=g) * 0.5
-    c = torch.randn((2, N, 256), device="cuda:0", generator=g) * 0.5
+    h = torch.randn((2, N, H), device="cuda:0", generator=g) * 0.5
+    c = torch.randn((2, N, H), device="cuda:0", generator=g) * 0.5
     col.h.copy_(h)
     col.c.copy_(c)
     col._forward(obs, 0)
@@ -210,9 +270,9 @@ def test_kernels_match_torch_fp32(voxnav):
     col.c.copy_(c)
     col._forward(obs, 1)
     assert torch.equal(col.actions[1].long(), lg.argmax(1))
-    # the rollout entry (vn_lstm_cell_masked): a step from the buffer's
-    # unmasked lstm_h / lstm_c[t] with episode_starts[t] is bitwise the step
-    # from the masked state through vn_lstm_cell
+    # the rollout entry (vn_lstm_fused_f32 with the start mask / vn_lstm_cell_masked):
+    # a step from the buffer's unmasked lstm_h / lstm_c[t] with episode_starts[t]
+    # is bitwise the step from the masked state through the plain entry
     col.deterministic = False
     start = (torch.rand(N, device="cuda:0", generator=g) < 0.3).float()
     keep = (start == 0)[None, :, None]
@@ -221,11 +281,73 @@ def test_kernels_match_torch_fp32(voxnav):
     col._starts[1].copy_(start)
     col._forward(obs, 1, in_rollout=True)
     hm, cm = col._hs[2].clone(), col._cs[2].clone()
+    am, vm, lm = col.actions[1].clone(), col.values[1].clone(), col.log_probs[1].clone()
     assert torch.equal(col._hs[1], h) and torch.equal(col._cs[1], c)     # inputs not written
     col.h.copy_(torch.where(keep, h, 0.0))
     col.c.copy_(torch.where(keep, c, 0.0))
     col._forward(obs, 2)
     assert torch.equal(hm, col.h) and torch.equal(cm, col.c)
+    if pid != "P0":     # the MLPs and heads run on the same h in both entries (same t_global: same draw)
+        assert torch.equal(am, col.actions[2]) and torch.equal(vm, col.values[2])
+        assert torch.equal(lm, col.log_probs[2])
+
+
+@pytest.mark.parametrize("pid", ["P0", "P2"])
+def test_act_without_stored_states_matches_oracle(voxnav, pid):
+    """``store_lstm_states=False`` (what voxnav.evaluate runs): 8 ``act()``
+    steps vs ``PolicyOracle.forward`` -- P0 on the ping-pong
+    vn_lstm_fused_f32 branch, P2 on torch.mm + vn_lstm_cell (unmasked) --
+    with an episode end after step 4, the (h, c) rows of the finished agents
+    zeroed by vn_collect_post_step.  Values, log-probs and hidden_state() at
+    the module's f32 bounds, every step."""
+    from oracle import collector_oracle as co
+    from voxnav.collector import RolloutCollector, _p
+    from voxnav.env import BatchedGridEnv
+    from voxnav.policy import numpy_weights
+    N, T = 64, 8
+    prod, _ = _rooms()
+    pol = _policy("lstm", None if pid == "P0" else pid)
+    env = BatchedGridEnv(num_agents=N, rooms=prod, local_map_length=4, device="cuda:0")
+    col = RolloutCollector(env, pol.to("cuda:0"), n_steps=1, sample_seed=1234, store_lstm_states=False, monitor=False)
+    _assert_path(col, pid)
+    assert not col.store and col._hs is None
+    orc = co.PolicyOracle(numpy_weights(pol))
+    rng = np.random.default_rng(17)
+    H = orc.H
+    h, c = np.zeros((2, N, H)), np.zeros((2, N, H))
+    starts = np.zeros(N)
+    for t in range(T):
+        obs = rng.random((N, 80)).astype(np.float32)
+        acts = col.act(torch.as_tensor(obs, device="cuda:0")).cpu().numpy()
+        logits, v, h, c = orc.forward(obs, h, c, starts)
+        starts = np.zeros(N)
+        lsm = co.log_softmax(logits)
+        _close(col.values[0].cpu(), v, 1e-4, 1e-4, f"values[{t}]")
+        _close(col.log_probs[0].cpu(), lsm[np.arange(N), acts], 1e-4, 1e-4, f"log_probs[{t}]")
+        gh, gc = col.hidden_state()
+        _close(gh.cpu(), h, 1e-4, 1e-4, f"h[{t}]")
+        _close(gc.cpu(), c, 1e-4, 1e-4, f"c[{t}]")
+        want = np.array([co.categorical_draw(lsm[n], co.sample_uniform(1234, n, t)) for n in range(N)])
+        mism = acts != want[:, 0]
+        assert np.all(want[mism, 1] < 1e-5) and mism.sum() <= 2
+        if t == 3:
+            # an episode end: terminated agents' state rows zeroed where act() reads them
+            starts = (rng.random(N) < 0.3).astype(np.float64)
+            assert 0 < starts.sum() < N
+            col._term.copy_(torch.as_tensor(starts.astype(np.uint8)))
+            col._trunc.zero_()
+            before = [x.clone() for x in col.hidden_state()]
+            voxnav._native.check(col.lib.vn_collect_post_step(
+                _p(col._term), _p(col._trunc), N, t, _p(col._starts[1]), None, None, None, None, None, None,
+                _p(col._tobs), env.obs_dim, _p(col.h[1]), 4, _p(col.c[1]), H, _p(col._stash_obs), _p(col._stash_h),
+                _p(col._stash_c), _p(col._stash_flat), col._stash_cap, _p(col._stash_cnt), _p(col.h), _p(col.c), None,
+                2, None), "vn_collect_post_step")
+            torch.cuda.synchronize()
+            done = torch.as_tensor(starts != 0, device="cuda:0")
+            assert np.array_equal(col._starts[1].cpu().numpy(), starts.astype(np.float32))
+            for x, x0 in zip(col.hidden_state(), before):
+                assert float(x[:, done].abs().max()) == 0.0 and torch.equal(x[:, ~done], x0[:, ~done])
+            assert int(col._stash_cnt.item()) == 0
 
 
 def test_compaction_and_episode_start(voxnav):
@@ -592,25 +714,6 @@ def test_linear_f32_bench_shape(voxnav, M, K, nout):
                 assert not bool(bad.any()), f"branch {i}: {int(bad.sum())} out of tolerance"
             else:
                 assert torch.equal(ty[i], ref.float()), f"branch {i}: identity form not exact"
-
-
-def _philox_u(seed, gids, t):
-    """The sampler's uniform (collector_oracle.sample_uniform) for many agents at once (numpy)."""
-    m = np.uint64(0xFFFFFFFF)
-    gids = np.asarray(gids, np.uint64)
-    hi = (int(t) | (1 << 63)) & ((1 << 64) - 1)
-    c0, c1 = gids & m, gids >> np.uint64(32)
-    c2 = np.full_like(gids, hi & 0xFFFFFFFF)
-    c3 = np.full_like(gids, hi >> 32)
-    k0, k1 = np.uint64(seed & 0xFFFFFFFF), np.uint64((seed >> 32) & 0xFFFFFFFF)
-    for r in range(10):
-        if r:
-            k0 = (k0 + np.uint64(0x9E3779B9)) & m
-            k1 = (k1 + np.uint64(0xBB67AE85)) & m
-        p0 = np.uint64(0xD2511F53) * c0
-        p1 = np.uint64(0xCD9E8D57) * c2
-        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & m, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & m
-    return (c0 >> np.uint64(8)).astype(np.float64) / 16777216.0
 
 
 def _mlp_head_ref(xs, layers, wa, ba, wv, bv):

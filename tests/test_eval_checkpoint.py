@@ -12,7 +12,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
-from helpers import oracle_env, product_room_set  # noqa: E402
+from helpers import oracle_env, path_policy, product_room_set  # noqa: E402
 
 
 def _policies():
@@ -68,18 +68,25 @@ def test_results_table_row_format():
 
 # ------------------------------------------------------------------ GPU
 @pytest.mark.gpu
-@pytest.mark.parametrize("kind", ["lstm", "mlp"])
+@pytest.mark.parametrize("kind", ["lstm", "mlp", "lstm-P0"])
 def test_evaluate_policy_matches_oracle_replay(kind):
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
     from oracle.collector_oracle import PolicyOracle
     from voxnav.evaluate import evaluate_policy
     from voxnav.policy import numpy_weights
-    pol = _policies()[kind]
+    if kind == "lstm-P0":
+        # the reference's policy shape (LSTM 256, [256, 256, 128]): evaluate's
+        # store_lstm_states=False collector on vn_lstm_fused_f32's ping-pong
+        # branch + vn_mlp_head_f32 (helpers.COLLECTOR_PATHS P0)
+        torch.manual_seed(3)
+        pol = path_policy("P0")
+    else:
+        pol = _policies()[kind]
     with torch.no_grad():
         pol.action_net.weight.mul_(300.0)      # decisive logits: argmax robust to f32 vs f64
     pol = pol.to("cuda:0")
-    src, L, n, seed = "set:P1_training", 4, 12, 100
+    src, L, n, seed = "set:P1_training", 4, 4 if kind == "lstm-P0" else 12, 100
     r = evaluate_policy(pol, product_room_set(src), n_episodes=n, local_map_length=L, seed=seed,
                         device="cuda:0", record_actions=True)
     acts = r["actions"]
