@@ -445,6 +445,33 @@ __device__ __forceinline__ Room load_room_c(const EnvConst *ec, int r) {
     return R;
 }
 
+// The end of an episode ("Goal Reached! Explored X % after N Steps" /
+// "Truncated after N Steps, with B Bumps and X % of cells discovered",
+// envs/CubicEnv.py:212-222): agent i's record (EpisodeRec, env_plan.h) takes
+// the counters the ending step left, before any auto-reset.  One lane per
+// agent calls it, from the rare episode-end branch only; the buffer's pointer
+// is read there from device memory (EnvConst), so the step loop holds nothing
+// for it.  A plain read-modify-write with vector loads and stores (the row
+// has one writer), inlined into that branch (neither an
+// out-of-line call nor a second branch for the no-auto-reset case).  flags:
+// EP_TERMINATED | EP_TRUNCATED.
+__device__ __forceinline__ void episode_end(const EnvConst *ec, int i, uint32_t steps, uint32_t bumps, uint32_t visited,
+                                         uint32_t max_steps, uint32_t room, uint32_t flags) {
+    EpisodeRec *r = reinterpret_cast<EpisodeRec *>(ec->episodes) + i;
+    r->episodes += 1u;
+    r->finished += flags & EP_TERMINATED;
+    r->sum_steps += steps;
+    r->sum_bumps += bumps;
+    r->sum_visited += visited;
+    r->sum_max_steps += max_steps;
+    r->last_steps = steps;
+    r->last_bumps = bumps;
+    r->last_visited = visited;
+    r->last_max_steps = max_steps;
+    r->last_room = room;
+    r->last_flags = flags;
+}
+
 // host: this translation unit's copy of the MT table (c_mt_g), once per device
 bool g_mt_ready[64] = {false};
 

@@ -2,7 +2,7 @@
 // hands the two kernel units: the launch parameters (Params), the
 // env-constant block the reset path reads from device memory (EnvConst), and
 // the units' host interfaces (vn_cubic: voxnav_env.hip, vn_simple:
-// voxnav_simple.hip, vn_state: voxnav_state.hip).  No device code and no
+// voxnav_simple.hip, vn_state: voxnav_state.hip, vn_episode: voxnav_episode.hip).  No device code and no
 // device symbol.  The structs are
 // in an anonymous namespace: each unit has its own (identical) copy, so
 // Params crosses the unit boundary as a pointer.
@@ -25,6 +25,7 @@ struct EnvConst {
     int n_rooms, use_room_draw, nby, pcache;
     uint32_t agent_bytes, xp_off, map_bytes, plane_bytes;   // plane_bytes: the planes a reset clears
     const uint4 *wimg;       // plane-set mode: per room, the bricked map with latent wall bits
+    uint4 *episodes;         // per agent one EpisodeRec (env_plan.h), 4 x 16 B; here and not in Params: read at episode ends only
 };
 
 struct Params {
@@ -97,6 +98,14 @@ namespace vn_state {
 int import_state(const void *params, const int64_t *state, const int8_t *belief, const uint8_t *mask, float *obs,
                  int32_t *n_rejected, int pw, int pd, hipStream_t s);
 }  // namespace vn_state
+
+// The episode records' unit (voxnav_episode.hip): the buffer the step kernels
+// update at episode ends (EnvConst::episodes), read out, reduced and cleared.
+namespace vn_episode {
+int records(const void *episodes, int N, int64_t *out, hipStream_t s);
+int totals(const void *episodes, int N, int64_t *out, hipStream_t s);
+int clear(void *episodes, int N, const uint8_t *mask, hipStream_t s);
+}  // namespace vn_episode
 
 // The simpleEnv unit (voxnav_simple.hip).
 namespace vn_simple {

@@ -60,6 +60,19 @@ constexpr int TAB_SREW = TAB_SIZE, TAB_SREW64 = TAB_SIZE + 16, TAB_ALL = TAB_SIZ
 // f32(a/5), f32(c/L)   (voxnav_env.hip, STAGE_WORDS)
 constexpr uint32_t TC_ZERO = 0x01u, TC_ONE = 0x02u, TC_ACT = 0x08u, TC_CID = 0x10u;
 
+// One agent's episode record (vn_episode_records): the totals over every
+// episode the agent ended since vn_create or the last vn_episode_clear, then
+// the last ended episode -- the state the ending step left, before any
+// auto-reset.  Written by lane q == 0 of the agent (CubicEnv) or the agent's
+// lane (simpleEnv) at the step that ends an episode (episode_end, env_core.h).
+struct EpisodeRec {
+    uint32_t episodes, finished;                             // finished: ended with `done` set
+    uint64_t sum_steps, sum_bumps, sum_visited, sum_max_steps;
+    uint32_t last_steps, last_bumps, last_visited, last_max_steps, last_room, last_flags;
+};
+static_assert(sizeof(EpisodeRec) == 64, "one 64-byte row per agent");
+constexpr uint32_t EP_TERMINATED = 1u, EP_TRUNCATED = 2u;    // last_flags
+
 // ----------------------------------------------------------------------------
 // The per-agent layout and kernel mode of one env: every value the host plans
 // once and hands to the kernels (Params, EnvConst) or reports (vn_get_info).
@@ -78,6 +91,7 @@ struct EnvLayout {
     int sline = 0;     // simpleEnv line layout (simple_line_kernel), rooms <= 32 x 32 x 8
     int defer = 0;     // CubicEnv byte-mark mode with deferred plane marks (PCM 3; rows <= 2 words)
     int pcache = 0;    // CubicEnv plane-set mode (PH 8, rooms <= 64 x 64): see pset_fill
+    uint32_t episode_bytes = (uint32_t)sizeof(EpisodeRec);   // both variants: the agent's episode record (own buffer)
 };
 
 inline EnvLayout plan_layout(int variant, int L, int maxW, int maxD, int maxH, const VnTuning &tun) {

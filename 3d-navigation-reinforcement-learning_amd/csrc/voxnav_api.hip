@@ -5,7 +5,8 @@
 // uploads the result and builds the env's Params once; a call copies that
 // Params, sets its own pointers and hands it to the variant's kernel unit
 // (vn_cubic: voxnav_env.hip, vn_simple: voxnav_simple.hip, the state import
-// vn_state: voxnav_state.hip; env_params.h).  The whole-env snapshots are
+// vn_state: voxnav_state.hip, the episode records vn_episode:
+// voxnav_episode.hip; env_params.h).  The whole-env snapshots are
 // host code here: device-to-device copies of the env's buffers under a tag.
 
 #include <atomic>
@@ -61,6 +62,7 @@ struct VnEnv {
     DevBuf wimg;      // plane-set mode: the latent-wall room images
     DevBuf stood;     // PCM 2: per agent 32 stood rows, then per agent the nonzero-set masks (uint2)
     DevBuf scratch;   // 8 KiB: targets of dummy output stores (the deferred flush's first step)
+    DevBuf episodes;  // per agent one EpisodeRec: totals and the last ended episode (vn_episode_records)
     size_t device_bytes = 0;
     Params params{};  // everything but the per-call fields (call_params), built once by vn_create
     bool wrec_written = false;    // the last step launch wrote every agent's window record (wrec_fill)
@@ -163,6 +165,8 @@ int alloc_buffers(VnEnv *e, const RoomTables &rt, size_t belief_alloc_bytes, boo
     if (!rc && l.pcache) rc = e->alloc(e->wimg, nr * VN_WIMG_REP * l.map_bytes);
     if (!rc && l.pcache == 2) rc = e->alloc(e->stood, n * 34u * sizeof(uint32_t));
     if (!rc) rc = e->alloc(e->scratch, 8192);
+    // after every other buffer: none of them moves (allocation placement alone swings the rate)
+    if (!rc) rc = e->alloc(e->episodes, n * (size_t)l.episode_bytes);
     return rc;
 }
 
@@ -185,6 +189,7 @@ hipError_t upload(VnEnv *e, const VnRoomSet &rooms, const RoomTables &rt, const 
     if (hipError_t he = hipMemset(p.err, 0, e->err.bytes)) return he;
     if (p.stood)
         if (hipError_t he = hipMemset(p.stood, 0, e->stood.bytes)) return he;
+    if (hipError_t he = hipMemset(e->episodes.ptr, 0, e->episodes.bytes)) return he;
     if (l.pcache) {
         std::vector<int8_t> img;
         wall_image(rooms, l, &img);
@@ -205,6 +210,7 @@ hipError_t upload(VnEnv *e, const VnRoomSet &rooms, const RoomTables &rt, const 
     ec.plane_bytes = l.plane_bytes;
     ec.pcache = l.pcache;
     ec.wimg = e->wimg.as<const uint4>();
+    ec.episodes = e->episodes.as<uint4>();
     if (hipError_t he = e->envc.put(&ec, sizeof(ec))) return he;
     return hipDeviceSynchronize();
 }
@@ -267,14 +273,17 @@ struct SnapPart {
 };
 
 // hot state with the window records behind it, next seeds, belief blocks,
-// goals, the simpleEnv draw-ahead, stood rows with the nonzero-set masks
-int snap_parts(const VnEnv *e, SnapPart out[6]) {
+// goals, the simpleEnv draw-ahead, the episode records, stood rows with the
+// nonzero-set masks
+constexpr int SNAP_MAX_PARTS = 7;
+int snap_parts(const VnEnv *e, SnapPart out[SNAP_MAX_PARTS]) {
     int n = 0;
     out[n++] = {e->hot.ptr, e->hot.bytes};
     out[n++] = {e->seed.ptr, e->seed.bytes};
     out[n++] = {e->params.belief, (size_t)e->lay.agent_bytes * (size_t)e->N};
     out[n++] = {e->goal.ptr, e->goal.bytes};
     out[n++] = {e->predraw.ptr, e->predraw.bytes};
+    out[n++] = {e->episodes.ptr, e->episodes.bytes};
     if (e->stood.ptr) out[n++] = {e->stood.ptr, e->stood.bytes};
     return n;
 }
@@ -305,6 +314,7 @@ uint64_t snapshot_tag(const VnEnv *e, const RoomTables &rt) {
         f.val<int32_t>(v);
     for (const uint32_t v : {l.map_bytes, l.agent_bytes, l.plane_bytes, l.xp_off, l.yp_off, l.sy_off, l.sz_off, l.qz_off})
         f.val<uint32_t>(v);
+    f.val<uint64_t>((uint64_t)e->episodes.bytes);   // the episode records travel with a snapshot
     f.val<int32_t>(e->tuning.pcache_cap);
     f.val<int32_t>(e->tuning.defer);
     f.val<int32_t>(e->tuning.simple_layout);
@@ -543,6 +553,24 @@ int vn_import_state(VnEnv *env, const int64_t *state, const int8_t *belief, cons
                                   (hipStream_t)stream);
 }
 
+int vn_episode_records(VnEnv *env, int64_t *out, void *stream) {
+    if (!env || !out) return fail(VN_ERR_INVALID, "NULL argument");
+    DeviceGuard dg(env->device);
+    return vn_episode::records(env->episodes.ptr, env->N, out, (hipStream_t)stream);
+}
+
+int vn_episode_totals(VnEnv *env, int64_t *out, void *stream) {
+    if (!env || !out) return fail(VN_ERR_INVALID, "NULL argument");
+    DeviceGuard dg(env->device);
+    return vn_episode::totals(env->episodes.ptr, env->N, out, (hipStream_t)stream);
+}
+
+int vn_episode_clear(VnEnv *env, const uint8_t *mask, void *stream) {
+    if (!env) return fail(VN_ERR_INVALID, "NULL argument");
+    DeviceGuard dg(env->device);
+    return vn_episode::clear(env->episodes.ptr, env->N, mask, (hipStream_t)stream);
+}
+
 int vn_snapshot_tag(const VnEnv *env, uint64_t *tag) {
     if (!env || !tag) return fail(VN_ERR_INVALID, "NULL argument");
     *tag = env->snap_tag;
@@ -551,7 +579,7 @@ int vn_snapshot_tag(const VnEnv *env, uint64_t *tag) {
 
 int vn_snapshot_bytes(const VnEnv *env, int64_t *bytes) {
     if (!env || !bytes) return fail(VN_ERR_INVALID, "NULL argument");
-    SnapPart parts[6];
+    SnapPart parts[SNAP_MAX_PARTS];
     const int n = snap_parts(env, parts);
     size_t total = 0;
     for (int k = 0; k < n; ++k) total += (parts[k].bytes + SNAP_ALIGN - 1) & ~(SNAP_ALIGN - 1);
@@ -562,7 +590,7 @@ int vn_snapshot_bytes(const VnEnv *env, int64_t *bytes) {
 int vn_snapshot_save(VnEnv *env, void *dst, void *stream) {
     if (!env || !dst) return fail(VN_ERR_INVALID, "NULL argument");
     DeviceGuard dg(env->device);
-    SnapPart parts[6];
+    SnapPart parts[SNAP_MAX_PARTS];
     const int n = snap_parts(env, parts);
     char *d = static_cast<char *>(dst);
     for (int k = 0; k < n; ++k) {
@@ -579,7 +607,7 @@ int vn_snapshot_load(VnEnv *env, const void *src, uint64_t tag, void *stream) {
                                     "another variant, size, layout, tuning, config or room set",
                     (unsigned long long)tag, (unsigned long long)env->snap_tag);
     DeviceGuard dg(env->device);
-    SnapPart parts[6];
+    SnapPart parts[SNAP_MAX_PARTS];
     const int n = snap_parts(env, parts);
     const char *s = static_cast<const char *>(src);
     for (int k = 0; k < n; ++k) {

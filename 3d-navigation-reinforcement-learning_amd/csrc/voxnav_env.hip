@@ -1608,7 +1608,7 @@ __global__ __launch_bounds__((PCM == 1 || PCM == 2) ? VN_PC_BLOCK : BLOCK,
     uint64_t ev4 = 0;                                     // STRIPE_R: reward events by slot (t & 3), 16 bits each
     const int kb = k;
     for (int j = 0; j < jn; ++j, ++k) {
-        bool finished = false;
+        bool finished = false, was_done = false;   // was_done: `done` entering the step (the no-auto-reset latch)
         const size_t row = (size_t)k * (size_t)p.N + (size_t)i;
         const uint64_t tt = tb + (uint64_t)j;
         if (active) {
@@ -1725,6 +1725,7 @@ __global__ __launch_bounds__((PCM == 1 || PCM == 2) ? VN_PC_BLOCK : BLOCK,
                     if (g.last_action == 2 && a == 2) ev |= 256u;
                 }
                 if (explored) ev |= 512u;
+                was_done = g.done;
                 if (g.visited >= R.finish_visits) {        // visited / total >= 0.84 (:212-215)
                     g.done = true;
                     ev |= 1024u;
@@ -1752,6 +1753,7 @@ __global__ __launch_bounds__((PCM == 1 || PCM == 2) ? VN_PC_BLOCK : BLOCK,
                 if (g.last_action == 2 && a == 2) r -= 0.5;
             }
             if (explored) r += 1.0;
+            was_done = g.done;
             if (g.visited >= R.finish_visits) {            // visited / total >= 0.84 (:212-215)
                 g.done = true;
                 r += 100.0;
@@ -1769,8 +1771,17 @@ __global__ __launch_bounds__((PCM == 1 || PCM == 2) ? VN_PC_BLOCK : BLOCK,
             }   // !STRIPE_R
         }
         ENV_T(3);
-        const bool need = p.autoreset && finished;
-        if (__ballot(need)) {
+        // an episode ends: with auto-reset at every finished step; without it at the first
+        // one after a reset only (an agent stepped on after its end entered the step with
+        // done set or step_count at max_steps, and records nothing more).  One rare branch
+        // for both: the record's read-modify-write, then the auto-reset.
+        const bool ends = finished && (p.autoreset || (!was_done && g.step_count - 1u < R.total_free));
+        if (__ballot(ends)) {
+            // the ended episode's record, from the state the step left (before the reset below)
+            if (ends && q == 0)
+                episode_end(p.envc, i, g.step_count, g.bumps, g.visited, R.total_free, (uint32_t)g.room,
+                            (g.done ? EP_TERMINATED : 0u) | (g.step_count >= R.total_free ? EP_TRUNCATED : 0u));
+            const bool need = ends && p.autoreset;
             const uint32_t seed = next_seed;
             group_reset<PH, PC, RT, SB, DM>(p, map, tile, dirty, pc_, ps, pdirty, need, seed, g, R, tab,
                                             need ? p.obs + row * VN_OBS_DIM : nullptr, wst, aslot, q, st, pend);

@@ -283,7 +283,7 @@ __global__ __launch_bounds__(64) void simple_kernel(Params p) {
             }
             if (p.actions_out) p.actions_out[(size_t)k * p.N + ai] = a;
         }
-        bool trunc = false, term = false;
+        bool trunc = false, term = false, was_done = false;   // was_done: `done` entering the step
         double r = 0.0;
         if (live) {
             // step (:109-150)
@@ -318,6 +318,7 @@ __global__ __launch_bounds__(64) void simple_kernel(Params p) {
             }
             if (a != 2 && a < 4) r += 0.05;                              // last_action == a here
             const int gx = goal & 0xff, gy = (goal >> 8) & 0xff, gz = (goal >> 16) & 0xff;
+            was_done = g.done;
             if (g.x == gx && g.y == gy && g.z >= gz && g.z - gz < 5) {   // SPOT_GOAL_HEIGTH = 5 (:201-206)
                 g.done = true;
                 r += 100.0;
@@ -336,8 +337,15 @@ __global__ __launch_bounds__(64) void simple_kernel(Params p) {
             }
         }
         // SB3 VecEnv auto-reset
-        const bool need = live && p.autoreset && (term || trunc);
-        if (__ballot(need)) {
+        // an episode ends: with auto-reset at every ending step; without it at the first one
+        // after a reset only (an agent stepped on after its end entered the step with done
+        // set or step_count at max_steps, and records nothing more)
+        const bool ends = live && (term || trunc) && (p.autoreset || (!was_done && g.step_count - 1u < R.total_free));
+        if (__ballot(ends)) {
+            if (ends)   // the ended episode's record, before the reset
+                episode_end(p.envc, ai, g.step_count, g.bumps, g.visited, R.total_free, (uint32_t)g.room,
+                            (term ? EP_TERMINATED : 0u) | (trunc ? EP_TRUNCATED : 0u));
+            const bool need = ends && p.autoreset;
             simple_reset_wave(p, map, need, next_seed, g, goal, R, row, lane, a0);
             if (need) next_seed += p.seed_stride;
         }
@@ -920,7 +928,7 @@ __global__ __launch_bounds__(128) void simple_pipe_kernel(Params p) {
     for (int k = 0; k < p.K; ++k) {
         const int b = k & 1;
         float *row = stage + b * 64 * OD + lane * OD;
-        bool trunc = false, term = false;
+        bool trunc = false, term = false, was_done = false;   // was_done: `done` entering the step
         int a = 0;
         bool moved = false, explored = false, seen = true;
         if (live) {
@@ -1013,6 +1021,7 @@ __global__ __launch_bounds__(128) void simple_pipe_kernel(Params p) {
             }
             if (a != 2 && a < 4) r += 0.05;
             const int gx = goal & 0xff, gy = (goal >> 8) & 0xff, gz = (goal >> 16) & 0xff;
+            was_done = g.done;
             if (g.x == gx && g.y == gy && g.z >= gz && g.z - gz < 5) {   // SPOT_GOAL_HEIGTH = 5 (:201-206)
                 g.done = true;
                 r += 100.0;
@@ -1031,8 +1040,16 @@ __global__ __launch_bounds__(128) void simple_pipe_kernel(Params p) {
         }
         SB_T(4);
         // SB3 VecEnv auto-reset
-        const bool need = live && p.autoreset && (term || trunc) && !(VN_ABLATE & 512u);
-        if (__ballot(need)) {
+        // an episode ends: with auto-reset at every ending step; without it at the first one
+        // after a reset only (an agent stepped on after its end entered the step with done
+        // set or step_count at max_steps, and records nothing more)
+        const bool ends = live && (term || trunc) && (p.autoreset || (!was_done && g.step_count - 1u < R.total_free)) &&
+                          !(VN_ABLATE & 512u);
+        if (__ballot(ends)) {
+            if (ends)   // the ended episode's record, before the reset
+                episode_end(p.envc, ai, g.step_count, g.bumps, g.visited, R.total_free, (uint32_t)g.room,
+                            (term ? EP_TERMINATED : 0u) | (trunc ? EP_TRUNCATED : 0u));
+            const bool need = ends && p.autoreset;
             sp_reset_wave<LMAX>(p, pl, need, live, next_seed, g, goal, R, w, row, lane, a0, nd,
                                 reinterpret_cast<uint32_t *>(sflg + 2 * 64));
             if (need) {
@@ -1363,7 +1380,7 @@ __global__ __launch_bounds__(128) void simple_line_kernel(Params p) {
     for (int k = 0; k < p.K; ++k) {
         const int b = k & 1;
         float *row = stage + b * 64 * OD + lane * OD;
-        bool trunc = false, term = false;
+        bool trunc = false, term = false, was_done = false;   // was_done: `done` entering the step
         int a = 0;
         bool moved = false, explored = false, seen = true;
         if (live) {
@@ -1442,6 +1459,7 @@ __global__ __launch_bounds__(128) void simple_line_kernel(Params p) {
             const int gx = goal & 0xff, gy = (goal >> 8) & 0xff, gz = (goal >> 16) & 0xff;
             const bool hit = g.x == gx && g.y == gy && g.z >= gz && g.z - gz < 5;   // SPOT_GOAL_HEIGTH = 5
             if (!moved) g.bumps += 1;
+            was_done = g.done;
             if (hit) g.done = true;
             const uint32_t ev = (moved ? 0u : 1u) | ((a != 2 && a < 4) ? 2u : 0u) | (hit ? 4u : 0u) |
                                 (explored ? 8u : 0u);
@@ -1457,8 +1475,16 @@ __global__ __launch_bounds__(128) void simple_line_kernel(Params p) {
         }
         SB_T(4);
         // SB3 VecEnv auto-reset
-        const bool need = live && p.autoreset && (term || trunc) && !(VN_ABLATE & 512u);
-        if (__ballot(need)) {
+        // an episode ends: with auto-reset at every ending step; without it at the first one
+        // after a reset only (an agent stepped on after its end entered the step with done
+        // set or step_count at max_steps, and records nothing more)
+        const bool ends = live && (term || trunc) && (p.autoreset || (!was_done && g.step_count - 1u < R.total_free)) &&
+                          !(VN_ABLATE & 512u);
+        if (__ballot(ends)) {
+            if (ends)   // the ended episode's record, before the reset
+                episode_end(p.envc, ai, g.step_count, g.bumps, g.visited, R.total_free, (uint32_t)g.room,
+                            (term ? EP_TERMINATED : 0u) | (trunc ? EP_TRUNCATED : 0u));
+            const bool need = ends && p.autoreset;
             sl_reset_wave<LMAX>(p, pl, need, live, next_seed, g, goal, R, w, row, lane, a0, nd, mt_lds, lx, ly);
             if (need) {
                 next_seed += p.seed_stride;

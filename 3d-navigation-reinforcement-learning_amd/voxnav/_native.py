@@ -18,6 +18,11 @@ VN_VARIANT_SIMPLE = 1
 VN_ABI_VERSION = 2
 VN_STATE_FIELDS = 16
 VN_MAX_L = 16
+VN_EPISODE_FIELDS = 12
+EPISODE_FIELDS = (
+    "episodes", "finished", "sum_steps", "sum_bumps", "sum_visited", "sum_max_steps",
+    "last_steps", "last_bumps", "last_visited", "last_max_steps", "last_room", "last_flags",
+)
 STATE_FIELDS = (
     "x", "y", "z", "facing", "last_action", "step_count", "visited_count", "bump_count",
     "done", "last_bump", "near_wall", "was_near_wall", "cells_insight_down", "room",
@@ -89,6 +94,9 @@ _SIGS = {
     "vn_snapshot_bytes": (C.c_int, [P, C.POINTER(C.c_int64)]),
     "vn_snapshot_save": (C.c_int, [P, P, P]),
     "vn_snapshot_load": (C.c_int, [P, P, C.c_uint64, P]),
+    "vn_episode_records": (C.c_int, [P, P, P]),
+    "vn_episode_totals": (C.c_int, [P, P, P]),
+    "vn_episode_clear": (C.c_int, [P, P, P]),
     "vn_gae": (C.c_int, [P, P, P, P, P, C.c_int32, C.c_int32, C.c_double, C.c_double, P, P, P]),
     "vn_lstm_cell": (C.c_int, [P, C.c_int64, P, P, P, P, P, P, P, C.c_int32, C.c_int32, C.c_int32, P]),
     "vn_policy_head": (C.c_int, [P, P, C.c_int32, C.c_int32, P, P, C.c_int32, P, P, C.c_uint64, C.c_uint64,

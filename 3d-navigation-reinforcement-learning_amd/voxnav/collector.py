@@ -313,7 +313,7 @@ class RolloutCollector:
         if self.recurrent:
             self._crit_hin = z(N, self.w.H, dt=torch.bfloat16 if self.fused else torch.float32)
             self._crit_c = z(N, self.w.H)
-        self.monitor = EpisodeMonitor(self.lib, N, T, dev) if monitor else None
+        self.monitor = EpisodeMonitor(self.lib, N, T, dev, env=env) if monitor else None
         self._r64 = z(N, dt=torch.float64) if monitor else None
         # learn() start: reset every env, episode_starts = ones, zero states
         self._obs[0] = env.reset(seed=reset_seed)

@@ -347,6 +347,34 @@ class BatchedGridEnv:
         _native.check(self.lib.vn_export_belief(self._h, _ptr(out), self._stream()), "vn_export_belief")
         return out
 
+    # ------------------------------------------------------- episode records
+    def episode_records(self) -> torch.Tensor:
+        """int64 [N, 12] (``_native.EPISODE_FIELDS``): per agent the totals
+        over every episode it ended since creation or the last clear
+        (``episodes``, ``finished``, ``sum_steps``, ``sum_bumps``,
+        ``sum_visited``, ``sum_max_steps``) and its last ended episode
+        (``last_steps``, ``last_bumps``, ``last_visited``, ``last_max_steps``,
+        ``last_room``, ``last_flags``: bit 0 terminated, bit 1 truncated) --
+        what envs/CubicEnv.py:212-222 prints at every episode end, written by
+        the step kernels before the auto-reset.  Stream-ordered, no host sync."""
+        out = torch.empty((self.num_agents, _native.VN_EPISODE_FIELDS), dtype=torch.int64, device=self.device)
+        _native.check(self.lib.vn_episode_records(self._h, _ptr(out), self._stream()), "vn_episode_records")
+        return out
+
+    def episode_totals(self) -> torch.Tensor:
+        """int64 [6]: the six totals of ``episode_records`` summed over all
+        agents on the device (exact integer sums)."""
+        out = torch.empty(6, dtype=torch.int64, device=self.device)
+        _native.check(self.lib.vn_episode_totals(self._h, _ptr(out), self._stream()), "vn_episode_totals")
+        return out
+
+    def clear_episode_records(self, mask: Optional[torch.Tensor] = None) -> None:
+        """Zero the episode records of the agents with ``mask[i]`` (None: all)."""
+        m = None
+        if mask is not None:
+            m = torch.as_tensor(mask).to(device=self.device, dtype=torch.uint8).reshape(self.num_agents).contiguous()
+        _native.check(self.lib.vn_episode_clear(self._h, _ptr(m), self._stream()), "vn_episode_clear")
+
     # ------------------------------------------------- state import, snapshots
     def import_state(self, state: torch.Tensor, belief: torch.Tensor, mask: Optional[torch.Tensor] = None,
                      out: Optional[torch.Tensor] = None, check: bool = True) -> torch.Tensor:

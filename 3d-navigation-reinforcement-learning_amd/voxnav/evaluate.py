@@ -49,7 +49,6 @@ def evaluate_policy(policy, rooms, n_episodes: int = 10, local_map_length: int =
         alive = torch.ones(n_episodes, dtype=torch.bool, device=dev)
         score = torch.zeros(n_episodes, dtype=torch.float64, device=dev)
         steps = torch.zeros(n_episodes, dtype=torch.int64, device=dev)
-        final = torch.zeros((n_episodes, 3), dtype=torch.int64, device=dev)   # bumps, visited, done
         limit = int(max_steps) if max_steps is not None else int(env.total_free_cells.max()) + 1
         acts: List[torch.Tensor] = []
         for t in range(limit):
@@ -61,11 +60,14 @@ def evaluate_policy(policy, rooms, n_episodes: int = 10, local_map_length: int =
             score += torch.where(alive, res.reward, torch.zeros_like(res.reward))
             steps += alive.to(torch.int64)
             ended = alive & (res.terminated.bool() | res.truncated.bool())
-            st = env.export_state()
-            final = torch.where(ended.view(-1, 1), st[:, [7, 6, 8]], final)
             alive &= ~ended
             if (t & 63) == 63 and not bool(alive.any()):
                 break
+        # bump_count / visited_count / done at each episode's end (:213-215): the step kernel
+        # recorded them at the ending step (no auto-reset here: the first ending step after
+        # the reset), read once; an agent that never ended within `limit` steps has a zero row
+        final = env.episode_records()[:, [7, 8, 11]]     # last_bumps, last_visited, last_flags
+        final[:, 2] &= 1                                 # bit 0: terminated = done
         f = final.cpu().tolist()
         sc, sp = score.cpu().tolist(), steps.cpu().tolist()
         eps = [dict(score=sc[i], bumps=f[i][0], discovered_cells=f[i][1], finished=bool(f[i][2]), steps=sp[i])

@@ -28,6 +28,14 @@ from .env import BatchedGridEnv
 from .spaces import Box, Discrete, EnvBase
 
 
+def _last_episode(env: BatchedGridEnv) -> Optional[dict]:
+    r = env.episode_records()[0].tolist()
+    if r[0] == 0:
+        return None
+    return {"steps": r[6], "bumps": r[7], "discovered_cells": r[8], "max_steps": r[9], "finished": bool(r[11] & 1),
+            "room": r[10], "terminated": bool(r[11] & 1), "truncated": bool(r[11] & 2)}
+
+
 class GridAgent(EnvBase):
     metadata = {"render_modes": ["human"]}
 
@@ -98,6 +106,14 @@ class GridAgent(EnvBase):
 
     def get_position(self):
         return (self.x, self.y, self.z)
+
+    @property
+    def last_episode(self) -> Optional[dict]:
+        """The last ended episode -- ``{"steps", "bumps", "discovered_cells",
+        "max_steps", "finished", "room", "terminated", "truncated"}``, the
+        figures the reference prints at an episode's end
+        (envs/CubicEnv.py:212-222) -- or None before the first episode end."""
+        return _last_episode(self._env)
 
     @property
     def internal_grid(self) -> np.ndarray:
@@ -207,6 +223,14 @@ class SimpleGridAgent(EnvBase):
 
     def get_position(self):
         return (self.x, self.y, self.z)
+
+    @property
+    def last_episode(self) -> Optional[dict]:
+        """The last ended episode -- ``{"steps", "bumps", "discovered_cells",
+        "max_steps", "finished", "room", "terminated", "truncated"}``, the
+        figures the reference prints at an episode's end
+        (envs/CubicEnv.py:212-222) -- or None before the first episode end."""
+        return _last_episode(self._env)
 
     @property
     def internal_grid(self) -> np.ndarray:

@@ -38,8 +38,15 @@ def _p(t: Optional[torch.Tensor]):
 
 
 class EpisodeMonitor:
-    def __init__(self, lib, n_agents: int, n_steps: int, device, info_buffer: int = 100):
+    def __init__(self, lib, n_agents: int, n_steps: int, device, info_buffer: int = 100, env=None):
         self.lib = lib
+        # the env whose device-side episode records (BatchedGridEnv.episode_totals) give the
+        # exploration metrics of each rollout; None: returns and lengths only
+        if env is not None and not hasattr(env.lib, "vn_episode_totals"):
+            env = None      # an older A/B build passed as lib= (load_variant) has no episode records
+        self.env = env
+        self.last_exploration: Optional[Dict[str, float]] = None
+        self._totals = env.episode_totals().tolist() if env is not None else None
         self.N = int(n_agents)
         self.T = int(n_steps)
         self.device = device
@@ -102,7 +109,34 @@ class EpisodeMonitor:
             for r, l, k in zip(rs, ls, ks):
                 when = t0 + (t1 - t0) * (k + 1) / T
                 self.ep_info_buffer.append({"r": round(r, 6), "l": int(l), "t": round(when - self.t_start, 6)})
+        self._harvest_exploration()
         return rec
+
+    def _harvest_exploration(self):
+        """The reference's episode-end figures (envs/CubicEnv.py:212-222,
+        train/evaluate_grid.py:213-247) over the episodes that ended since the
+        previous harvest: one read of the env's device-side totals,
+        differenced.  ``last_exploration`` is None when no episode ended, else
+
+        * ``ep_finished_rate``   = finished episodes / episodes
+        * ``ep_bumps_mean``      = bumps / episodes
+        * ``ep_discovered_mean`` = discovered cells / episodes
+        * ``ep_coverage``        = discovered cells / max_steps, a ratio of
+          the two SUMS over those episodes (not the mean of per-episode ratios).
+
+        These cover this rollout's episodes, not SB3's last-100 window."""
+        if self.env is None:
+            return
+        tot = self.env.episode_totals().tolist()
+        d = [a - b for a, b in zip(tot, self._totals)]
+        self._totals = tot
+        n = d[0]
+        if n <= 0:          # none ended (or the records were cleared)
+            self.last_exploration = None
+            return
+        self.last_exploration = {"ep_finished_rate": d[1] / n, "ep_bumps_mean": d[3] / n,
+                                 "ep_discovered_mean": d[4] / n,
+                                 "ep_coverage": d[4] / d[5] if d[5] > 0 else 0.0}
 
     def ep_rew_mean(self) -> Optional[float]:
         if not self.ep_info_buffer:

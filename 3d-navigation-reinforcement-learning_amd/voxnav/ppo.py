@@ -471,7 +471,12 @@ def learn(collector, learner: PPOLearner, total_timesteps: int, callback=None) -
     Returns the per-iteration stats: the train losses, ``num_timesteps``,
     the Monitor's ``ep_rew_mean`` / ``ep_len_mean`` over the last 100
     finished episodes (SB3's ``rollout/`` logger keys, when any episode has
-    finished) and the evaluation's ``eval/*`` keys when one ran."""
+    finished), for a rollout in which at least one episode ended the
+    reference's episode-end figures over that rollout's episodes --
+    ``ep_finished_rate``, ``ep_bumps_mean``, ``ep_discovered_mean`` and
+    ``ep_coverage`` (discovered cells / max_steps as a ratio of the two sums;
+    ``EpisodeMonitor._harvest_exploration``) -- and the evaluation's
+    ``eval/*`` keys when one ran."""
     if collector.policy is not learner.policy:
         raise ValueError("collector and learner must share the policy module")
     cbs = [] if callback is None else (list(callback) if isinstance(callback, (list, tuple)) else [callback])
@@ -492,6 +497,8 @@ def learn(collector, learner: PPOLearner, total_timesteps: int, callback=None) -
         if mon is not None and mon.ep_info_buffer:
             st["ep_rew_mean"] = mon.ep_rew_mean()
             st["ep_len_mean"] = mon.ep_len_mean()
+        if mon is not None and getattr(mon, "last_exploration", None):
+            st.update(mon.last_exploration)   # this rollout's episodes: ep_finished_rate, ep_bumps_mean, ...
         st.update(evals)
         history.append(st)
         stop = False

@@ -26,7 +26,10 @@ oracle's auto-reset replay):
   ``"terminal_observation"`` (the last obs of the finished episode; ``obs``
   then holds the next episode's first one) and the Monitor's
   ``"episode": {"r": round(sum of f64 rewards, 6), "l": length,
-  "t": round(seconds since the monitor started, 6)}``;
+  "t": round(seconds since the monitor started, 6)}``, and on done
+  ``"exploration": {"steps", "bumps", "discovered_cells", "max_steps",
+  "finished", "room"}``, the finished episode's figures the reference prints
+  at its end (envs/CubicEnv.py:212-222), from the device-side episode records;
 * ``seed``, ``close``, ``get_attr`` / ``set_attr`` / ``env_method`` /
   ``env_is_wrapped`` for the attributes SB3 and Grid_Train read
   (``visited_count``, ``bump_count``, ``total_free_cells``, ``done``,
@@ -88,6 +91,13 @@ def build_infos(terminated: np.ndarray, truncated: np.ndarray, terminal_obs: Opt
                 d["terminal_observation"] = terminal_obs[i]
     assert len(infos) == n
     return infos
+
+
+def exploration_info(rec_row) -> dict:
+    """``info["exploration"]`` of a finished env from its episode-record row
+    (``BatchedGridEnv.episode_records``): the last ended episode."""
+    return {"steps": int(rec_row[6]), "bumps": int(rec_row[7]), "discovered_cells": int(rec_row[8]),
+            "max_steps": int(rec_row[9]), "finished": bool(int(rec_row[11]) & 1), "room": int(rec_row[10])}
 
 
 class VoxnavVecEnv(_VecEnvBase):
@@ -190,6 +200,12 @@ class VoxnavVecEnv(_VecEnvBase):
         ep_r = mon.rec_return[0].cpu().numpy() if mon is not None else None
         ep_l = mon.rec_length[0].cpu().numpy() if mon is not None else None
         infos = build_infos(te, tr, tobs, ep_r, ep_l, time.time() - mon.t_start if mon is not None else 0.0)
+        if done.any():
+            # the finished episodes' steps / bumps / discovered cells (envs/CubicEnv.py:212-222):
+            # the kernel recorded them before the auto-reset; read only on such steps
+            rec = self.env.episode_records().cpu().numpy()
+            for i in np.flatnonzero(done).tolist():
+                infos[i]["exploration"] = exploration_info(rec[i])
         if mon is not None and done.any():
             for i in np.flatnonzero(done).tolist():
                 mon.ep_info_buffer.append(infos[i]["episode"])

@@ -264,7 +264,8 @@ int vn_import_state(VnEnv *env, const int64_t *state, const int8_t *belief, cons
  * Whole-env raw snapshots (both variants, every layout): an opaque,
  * layout-native copy of every mutable per-agent buffer -- the hot state with
  * the window records behind it, the next seeds, the belief blocks, the
- * goals, the simpleEnv draw-ahead, the stood rows and masks -- as
+ * goals, the simpleEnv draw-ahead, the episode records, the stood rows and
+ * masks -- as
  * stream-ordered device-to-device copies into / from one caller-owned device
  * blob of vn_snapshot_bytes bytes.  The blob has no header: no call reads
  * device memory back.  What its bytes mean is named by vn_snapshot_tag, a
@@ -281,6 +282,43 @@ int vn_snapshot_tag(const VnEnv *env, uint64_t *tag);
 int vn_snapshot_bytes(const VnEnv *env, int64_t *bytes);
 int vn_snapshot_save(VnEnv *env, void *dst, void *stream);
 int vn_snapshot_load(VnEnv *env, const void *src, uint64_t tag, void *stream);
+
+/*
+ * Episode records (both variants): what the reference reports at every
+ * episode end -- "Goal Reached! Explored X % after N Steps" / "Truncated
+ * after N Steps, with B Bumps and X % of cells discovered"
+ * (envs/CubicEnv.py:212-222) -- and what train/evaluate_grid.py:213-247
+ * builds its results table from: steps, bumps, discovered cells, finished.
+ * The step kernels write one 64-byte row per agent at the step that ends an
+ * episode, from the state that step left (vn_export_state's fields 5, 7, 6,
+ * 14, 13 and `done`), before the in-kernel auto-reset overwrites it; the
+ * totals survive any number of episode ends inside one fused launch.
+ *
+ * An episode ends at the first step after a reset on which terminated or
+ * truncated is set.  With autoreset every such step ends one.  Without it an
+ * agent that is stepped on after its end records nothing more until it is
+ * reset (the reference keeps returning truncated there): a step whose
+ * entering state had `done` set or step_count at max_steps does not count.
+ * vn_reset of an agent in mid-episode abandons that episode (nothing is
+ * counted); vn_import_state leaves the rows untouched; vn_snapshot_save /
+ * vn_snapshot_load carry them.  `finished` counts the episodes that ended
+ * with `done` set (CubicEnv: the finish percentage reached; simpleEnv: goal
+ * reached).  last_flags: bit 0 terminated, bit 1 truncated.  Rows are zero at
+ * vn_create.  All three calls are stream-ordered and do not synchronise the
+ * host.
+ */
+#define VN_EPISODE_FIELDS 12
+/* device i64 [N][12]: episodes, finished, sum_steps, sum_bumps, sum_visited,
+   sum_max_steps, last_steps, last_bumps, last_visited, last_max_steps,
+   last_room, last_flags   (envs/CubicEnv.py:212-222) */
+int vn_episode_records(VnEnv *env, int64_t *out, void *stream);
+/* device i64 [6]: the six totals summed over all agents, reduced on the
+   device (exact integer sums, so order-independent and reproducible): the
+   per-run aggregates of train/evaluate_grid.py:213-247 */
+int vn_episode_totals(VnEnv *env, int64_t *out, void *stream);
+/* zero the rows of agents with mask[i] != 0 (NULL = all): a new measuring
+   window (train/evaluate_grid.py:213-247 starts each table from zero) */
+int vn_episode_clear(VnEnv *env, const uint8_t *mask, void *stream);
 
 /*
  * GAE advantage/return scan (SB3 RolloutBuffer.compute_returns_and_advantage,
