@@ -423,20 +423,45 @@ __device__ __forceinline__ const int8_t *room_image(const int8_t *wimg, int room
     return wimg + ((size_t)room * VN_WIMG_REP + (VN_WIMG_REP > 1 ? agent % VN_WIMG_REP : 0u)) * map_bytes;
 }
 
-// The window bytes [z - 2, z + 1] of a tile column as one u32 (byte 0 = z - 2,
-// zeros outside [0, PH)): two dword reads and a funnel shift, so a sensing
-// pass holds one register per window column instead of the whole column
-// (PH 16: 4 registers per column).
+// The window bytes [z - 2, z + 1] (byte 0 = z - 2, zeros outside [0, PH)) of
+// the 4 tile columns in slots s[0..3], one u32 each, and the whole column of
+// slot s[2] (dx = 0; lane 2's center column).  One LDS phase: every read is
+// issued before the first result is used and nothing here branches, so the
+// step pays one LDS round trip for the window instead of one per dword.
+// Each window word comes from one 8-byte piece of its column (PH 8: the
+// column, which for slot s[2] is also the center column; else the two dwords
+// from z - 2 on, clamped into the column, one two-dword read) and one shift
+// that zero-fills below byte 0 and above byte PH - 1; so a sensing pass still
+// holds one register per window column, not the column.
 template <int PH>
-__device__ __forceinline__ uint32_t tile_win(const uint64_t *tile, int slot, int z) {
+__device__ __forceinline__ void tile_win4(const uint64_t *tile, const int (&s)[4], int z, uint32_t (&win)[4],
+                                          Col<PH> &cen) {
     constexpr int NW = PH / 4;
-    const uint32_t *cw = reinterpret_cast<const uint32_t *>(tile + slot * TileGeom<PH>::QW);
-    const int o = z - 2;
+    const int o = z - 2;                                     // -2 .. PH - 3
     const int k0 = o >> 2;                                   // -1 for o = -2, -1
-    const uint32_t lo = cw[k0 < 0 ? 0 : k0] & (k0 >= 0 ? ~0u : 0u);
-    const uint32_t hi = cw[k0 + 1 < NW ? k0 + 1 : NW - 1] & (k0 + 1 < NW ? ~0u : 0u);
-    const int sh = (o & 3) * 8;
-    return sh ? (lo >> sh) | (hi << (32 - sh)) : lo;
+    const int b = NW == 2 ? 0 : (k0 < 0 ? 0 : k0 > NW - 2 ? NW - 2 : k0);   // first dword of the piece
+    const int rel = o - 4 * b;                               // window start in the piece: -2 .. 7
+    const int l = rel < 0 ? -8 * rel : 0, r = rel < 0 ? 0 : 8 * rel;
+    auto piece = [&](int i) -> uint64_t {
+        if constexpr (PH == 8) {
+            return tile[s[i]];
+        } else {
+            const uint32_t *cw = reinterpret_cast<const uint32_t *>(tile + s[i] * TileGeom<PH>::QW) + b;
+            return (uint64_t)cw[0] | ((uint64_t)cw[1] << 32);
+        }
+    };
+    auto word = [&](uint64_t v) -> uint32_t { return rel < 0 ? (uint32_t)v << l : (uint32_t)(v >> r); };
+    uint64_t v[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) v[i] = piece(i);
+    if constexpr (PH == 8) cen.w[0] = v[2];
+    else tile_read<PH>(tile, s[2], cen);
+    // the phase's reads (the caller's plane-row word included) stay ahead of
+    // everything below: the scheduler would otherwise sink one of them past
+    // the ray record's wait, a round trip of its own
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) win[i] = word(v[i]);
 }
 
 // byte z of a tile column
@@ -836,18 +861,24 @@ __device__ __forceinline__ int sense_observe(const Params &p, int8_t *map, uint6
     };
     uint32_t win[4];
     Col<PH> cen;
+    // PC: the lane's plane-row word, read in the same LDS phase as the window
+    // (every lane reads: lanes 2 / 3 the words of lanes 0 / 1, unused)
+    RT prw = 0;
+    if constexpr (PC) prw = ps[((q & 1) == 0 ? (y & 3) : 4 + (x & 3)) * 8 + z];
+    if constexpr (FRESH) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if (FRESH) {
+        for (int i = 0; i < 4; ++i) {
             Col<PH> c;
             fresh_col(i, c);
             win[i] = col_window<PH>(c, z);
             if (i == 2) cen = c;
-        } else {
-            win[i] = tile_win<PH>(tile, tslot(x + i - 2, cy), z);
         }
+    } else {
+        // one LDS phase, ahead of the first use of the ray record: its load's
+        // latency and the LDS round trip overlap
+        const int ws[4] = {tslot(x - 2, cy), tslot(x - 1, cy), tslot(x, cy), tslot(x + 1, cy)};
+        tile_win4<PH>(tile, ws, z, win, cen);
     }
-    if (!FRESH) tile_read<PH>(tile, tslot(x, cy), cen);
     uint32_t chg = 0;                     // bit i: window column i changed by this pass
 
     // ---- ray extents from the room's 8-byte record (bit7: ended at a wall) ----
@@ -886,7 +917,7 @@ __device__ __forceinline__ int sense_observe(const Params &p, int8_t *map, uint6
             pm[w] = (w == 0 || pw0 + 1 <= pwend) && hi >= lo ? ((~0ull) >> (63 - (hi - lo))) << lo : 0ull;
         }
         if (PC) {                          // nw == 1: the row word is in LDS
-            pc_.w[0] = *prow_lds;
+            pc_.w[0] = prw;
             pc_.w[1] = 0ull;
             pc_.w0 = 0;
         } else if (FRESH) {                // planes were cleared by the reset
@@ -1405,7 +1436,9 @@ __global__ __launch_bounds__((PCM == 1 || PCM == 2) ? VN_PC_BLOCK : BLOCK,
     for (int k = threadIdx.x; k < TAB_SIZE; k += blockDim.x) tab[k < 256 ? tab_ix((uint32_t)k) : k] = p.lut[k];
     __syncthreads();
     // a wave without agents leaves (no block-wide barrier follows)
-    const int wave_agent0 = (int)((blockIdx.x * blockDim.x + (threadIdx.x & ~63)) / GROUP);
+    // (wave-uniform: a scalar, so the flush's row block address costs no VGPR)
+    const int wave_agent0 =
+        __builtin_amdgcn_readfirstlane((int)((blockIdx.x * blockDim.x + (threadIdx.x & ~63)) / GROUP));
     if (wave_agent0 >= p.N) return;
 
     uint64_t *tile = tiles + (threadIdx.x / GROUP) * TileGeom<PH>::STRIDE;
