@@ -386,41 +386,21 @@ typedef float F4v __attribute__((ext_vector_type(4)));
 // 0xC0 (unknown, latent wall, free, wall) would all sit in LDS bank 0 and a
 // 32-lane lookup would serialise over them; XOR-ing the low 2 bits with the
 // top 2 puts them in banks 0-3 (a permutation inside every aligned 4-group).
-#ifndef VN_TAB_SWZ
-#define VN_TAB_SWZ 1
-#endif
-__device__ __forceinline__ uint32_t tab_ix(uint32_t b) { return VN_TAB_SWZ ? b ^ ((b >> 6) & 3u) : b; }
+__device__ __forceinline__ uint32_t tab_ix(uint32_t b) { return b ^ ((b >> 6) & 3u); }
 
 // float4 of a code word (4 belief bytes or tail codes): 4 LUT lookups
 __device__ __forceinline__ float4 code_float4(uint32_t wb, const float *tab) {
-    if (VN_TAB_SWZ) wb ^= (wb >> 6) & 0x03030303u;        // tab_ix of all 4 bytes
+    wb ^= (wb >> 6) & 0x03030303u;        // tab_ix of all 4 bytes
     return make_float4(tab[wb & 0xffu], tab[(wb >> 8) & 0xffu], tab[(wb >> 16) & 0xffu], tab[wb >> 24]);
 }
 
-// Streaming store of one obs float4 to HBM.  VN_OBS_STORE: 0 plain, 1
-// non-temporal, 2 sc1 (write-through; the line is dropped from L2, so the
-// obs stream does not evict the belief / plane / ray-table lines), 3 sc1 nt,
-// 4 sc0 sc1 nt.  Measured (scripts/ab.py, 65536 agents, 32x32x8, 5408
-// steps, 7 rounds): 1 = 6.83, 3 = 6.86, 4 = 6.65 G env-steps/s -- equal
-// within noise; 0 and 2 are ~15% slower.  1 stays the default.
-#ifndef VN_OBS_STORE
-#define VN_OBS_STORE 1
-#endif
+// Streaming store of one obs float4 to HBM: non-temporal.  Measured against
+// the other store flavours at the time (scripts/ab.py, 65536 agents, 32x32x8,
+// 5408 steps, 7 rounds): non-temporal 6.83, sc1 nt 6.86, sc0 sc1 nt 6.65
+// G env-steps/s -- equal within noise; a plain store and sc1 alone (write-
+// through, the line dropped from L2) were ~15% slower.
 __device__ __forceinline__ void obs_store(float4 *dst, const float4 &v) {
-#if VN_OBS_STORE == 1
     __builtin_nontemporal_store(F4v{v.x, v.y, v.z, v.w}, reinterpret_cast<F4v *>(dst));
-#elif VN_OBS_STORE == 2
-    const F4v w{v.x, v.y, v.z, v.w};
-    asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(dst), "v"(w) : "memory");
-#elif VN_OBS_STORE == 3
-    const F4v w{v.x, v.y, v.z, v.w};
-    asm volatile("global_store_dwordx4 %0, %1, off sc1 nt" ::"v"(dst), "v"(w) : "memory");
-#elif VN_OBS_STORE == 4
-    const F4v w{v.x, v.y, v.z, v.w};
-    asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1 nt" ::"v"(dst), "v"(w) : "memory");
-#else
-    *dst = v;
-#endif
 }
 typedef __attribute__((address_space(3))) F4v LdsF4;     // LDS
 typedef __attribute__((address_space(1))) F4v GlbF4;     // global

@@ -20,15 +20,12 @@
 // with every knob at its default: a knob set without VN_DIAG does not build.
 #ifndef VN_DIAG
 #if defined(VN_ABLATE) || defined(VN_ENV_PROF) || defined(VN_SIMPLE_PROF) || defined(VN_LF_DIAG) || \
-    defined(VN_PF_DIAG) || defined(VN_LDS_PAD_U64) || defined(VN_PHILOX16) || defined(VN_REWARD_STRIPE) || \
-    defined(VN_PC_BLOCK) || defined(VN_PC_MIN_WAVES) || defined(VN_MIN_WAVES_PER_SIMD) || defined(VN_PREMOVE) || \
-    defined(VN_STAGE_OBS) || defined(VN_LF_ROWS) || defined(VN_LF_KC) || defined(VN_LF_RAW_BARRIER) || \
-    defined(VN_LF_MIN_WAVES) || defined(VN_LF_WPE) || defined(VN_STOOD) || defined(VN_DPP) || \
-    defined(VN_TAB_SWZ) || defined(VN_PF_FAST) || defined(VN_PF_PREF) || defined(VN_OBS_STORE) || \
-    defined(VN_LDS_BARRIER) || defined(VN_ROW_WB) || defined(VN_SETPRIO) || \
-    defined(VN_SETPRIO_FLUSH) || defined(VN_ENV_WT) || defined(VN_DFLUSH_DEFAULT) || defined(VN_STOOD_PART) || defined(VN_WIMG_REP) || \
-    defined(VN_BRICK_T) || defined(VN_WREC_K_DEFAULT) || defined(VN_WREC) || defined(VN_DM_CODES) || defined(VN_GEMM_ASM) || \
-    defined(VN_ROWS_RAWBAR) || defined(VN_ROWS_PRELOAD) || defined(VN_ROWS_FLAGS)
+    defined(VN_PF_DIAG) || defined(VN_LDS_PAD_U64) || defined(VN_PC_BLOCK) || defined(VN_PC_MIN_WAVES) || \
+    defined(VN_MIN_WAVES_PER_SIMD) || defined(VN_LF_ROWS) || defined(VN_LF_KC) || defined(VN_LF_RAW_BARRIER) || \
+    defined(VN_LF_MIN_WAVES) || defined(VN_LF_WPE) || defined(VN_PF_FAST) || defined(VN_PF_PREF) || \
+    defined(VN_LDS_BARRIER) || defined(VN_ENV_WT) || defined(VN_DFLUSH_DEFAULT) || defined(VN_WIMG_REP) || \
+    defined(VN_BRICK_T) || defined(VN_WREC_K_DEFAULT) || defined(VN_GEMM_ASM) || defined(VN_ROWS_RAWBAR) || \
+    defined(VN_ROWS_PRELOAD) || defined(VN_ROWS_FLAGS)
 #error "compile-time knobs are for the diagnostics build only (define VN_DIAG)"
 #endif
 #endif
