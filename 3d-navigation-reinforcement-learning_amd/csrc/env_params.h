@@ -107,6 +107,16 @@ int totals(const void *episodes, int N, int64_t *out, hipStream_t s);
 int clear(void *episodes, int N, const uint8_t *mask, hipStream_t s);
 }  // namespace vn_episode
 
+// The per-agent gather (voxnav_gather.hip; vn_copy_agents): agent i of `dst`
+// becomes a copy of agent src_index[i] of `src` -- both complete Params of
+// layout-compatible envs (the caller has compared their layout tags), `parts`
+// their AgentParts (env_plan.h).  Zeroes *n_rejected (when given) on the
+// stream, then one launch.
+namespace vn_gather {
+int copy_agents(const void *dst, const void *src, const void *parts, const int32_t *src_index, const int64_t *seeds,
+                int32_t *n_rejected, hipStream_t s);
+}  // namespace vn_gather
+
 // The simpleEnv unit (voxnav_simple.hip).
 namespace vn_simple {
 int ensure_mt(int device);

@@ -156,6 +156,56 @@ inline EnvLayout plan_layout(int variant, int L, int maxW, int maxD, int maxH, c
 }
 
 // ----------------------------------------------------------------------------
+// One agent's share of every mutable per-agent buffer, in bytes (0: the env
+// has no such buffer).  The whole-env snapshots (voxnav_api.hip, snap_parts)
+// and the per-agent gather (voxnav_gather.hip) both size their copies from
+// this plan, so a buffer added here reaches both.  Each buffer is an array of
+// N such rows, except that `wrec` follows the N hot words in the hot state's
+// allocation and `pnz` follows the N stood blocks in theirs.
+// ----------------------------------------------------------------------------
+struct AgentParts {
+    uint32_t hot = 0;       // the hot word
+    uint32_t wrec = 0;      // CubicEnv: the window record, 16 columns x PH bytes
+    uint32_t seed = 0;      // the next auto-reset seed
+    uint32_t belief = 0;    // the belief block (EnvLayout::agent_bytes)
+    uint32_t goal = 0;      // the goal word (allocated in both variants; simpleEnv uses it)
+    uint32_t predraw = 0;   // the draw-ahead row (allocated in both variants; simpleEnv uses it)
+    uint32_t stood = 0;     // plane-set mode 2: 32 stood rows
+    uint32_t pnz = 0;       // plane-set mode 2: the nonzero-set mask (uint2)
+    uint32_t episode = 0;   // the episode record: in a snapshot, not in a per-agent copy
+    // what a per-agent copy moves
+    uint32_t copied() const { return hot + wrec + seed + belief + goal + predraw + stood + pnz; }
+};
+
+inline AgentParts agent_parts(const EnvLayout &l) {
+    AgentParts a;
+    a.hot = 16u;
+    a.wrec = l.variant != VN_VARIANT_SIMPLE ? 16u * (uint32_t)l.ph : 0u;
+    a.seed = 4u;
+    a.belief = l.agent_bytes;
+    a.goal = 4u;
+    a.predraw = 16u;
+    if (l.variant != VN_VARIANT_SIMPLE && l.pcache == 2) {
+        a.stood = 32u * 4u;
+        a.pnz = 8u;
+    }
+    a.episode = l.episode_bytes;
+    return a;
+}
+
+// The snapshot blob: the allocations in snap_parts' order (hot words + window
+// records, seeds, belief blocks, goals, draw-ahead rows, episode records,
+// stood rows + masks), each rounded up to SNAP_ALIGN bytes.
+constexpr size_t SNAP_ALIGN = 256;
+inline size_t snap_up(size_t bytes) { return (bytes + SNAP_ALIGN - 1) & ~(SNAP_ALIGN - 1); }
+inline size_t snapshot_bytes(const AgentParts &a, size_t n) {
+    size_t total = snap_up(n * (a.hot + a.wrec)) + snap_up(n * a.seed) + snap_up(n * a.belief) + snap_up(n * a.goal) +
+                   snap_up(n * a.predraw) + snap_up(n * a.episode);
+    if (a.stood) total += snap_up(n * (a.stood + a.pnz));
+    return total;
+}
+
+// ----------------------------------------------------------------------------
 // rooms -> descriptors, ray records, start lists
 // ----------------------------------------------------------------------------
 struct RayRec {   // 8 bytes, uploaded as the kernels' uint2: x = the +x,-x,+y,-y runs, y = +z,-z runs | wall<<16 | edge<<17

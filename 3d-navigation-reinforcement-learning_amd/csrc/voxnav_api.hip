@@ -6,8 +6,10 @@
 // Params, sets its own pointers and hands it to the variant's kernel unit
 // (vn_cubic: voxnav_env.hip, vn_simple: voxnav_simple.hip, the state import
 // vn_state: voxnav_state.hip, the episode records vn_episode:
-// voxnav_episode.hip; env_params.h).  The whole-env snapshots are
-// host code here: device-to-device copies of the env's buffers under a tag.
+// voxnav_episode.hip, the per-agent gather vn_gather: voxnav_gather.hip;
+// env_params.h).  The whole-env snapshots are host code here: device-to-device
+// copies of the env's buffers under a tag; the per-agent copies between envs
+// (vn_copy_agents) are checked here against the layout tag and run by vn_gather.
 
 #include <atomic>
 #include <cstdlib>
@@ -67,6 +69,8 @@ struct VnEnv {
     Params params{};  // everything but the per-call fields (call_params), built once by vn_create
     bool wrec_written = false;    // the last step launch wrote every agent's window record (wrec_fill)
     uint64_t snap_tag = 0;        // hash of everything that decides what a snapshot's bytes mean (snapshot_tag)
+    uint64_t layout_tag = 0;      // ... and of what decides one agent's bytes: the same without N, agent_id_base and
+                                  // the episode buffer's size (vn_copy_agents)
 
     int alloc(DevBuf &b, size_t bytes) {
         const hipError_t he = hipMalloc(&b.ptr, bytes);
@@ -135,13 +139,14 @@ constexpr int32_t kOptionMax[vn_detail::N_OPTIONS] = {2, 1, 1, 1};
 // allocation (first failure: VN_ERR_OOM) ...
 int alloc_buffers(VnEnv *e, const RoomTables &rt, size_t belief_alloc_bytes, bool belief_contig) {
     const EnvLayout &l = e->lay;
+    const AgentParts ap = agent_parts(l);   // the per-agent buffers' row sizes (env_plan.h)
     const size_t n = (size_t)e->N, nr = rt.total_free.size();
     int rc = e->alloc(e->rooms, rt.desc.size() * sizeof(uint32_t));
     if (!rc) rc = e->alloc(e->rays, rt.rays.size() * sizeof(RayRec));
     if (!rc) rc = e->alloc(e->starts, rt.starts.size() * sizeof(uint32_t));
     if (!rc) rc = e->alloc(e->lut, TAB_ALL * sizeof(float));
-    if (!rc) rc = e->alloc(e->hot, n * (sizeof(uint4) + (l.variant != VN_VARIANT_SIMPLE ? 16u * (size_t)l.ph : 0u)));
-    if (!rc) rc = e->alloc(e->seed, n * sizeof(uint32_t));
+    if (!rc) rc = e->alloc(e->hot, n * ((size_t)ap.hot + ap.wrec));
+    if (!rc) rc = e->alloc(e->seed, n * ap.seed);
     // The belief maps.  A VMM-mapped variant (hipMemCreate / hipMemMap
     // chunks) was measured in round 6 and removed: on that memory the
     // kernels' results differed from the oracle, and it did not remove the
@@ -160,13 +165,13 @@ int alloc_buffers(VnEnv *e, const RoomTables &rt, size_t belief_alloc_bytes, boo
     }
     if (!rc) rc = e->alloc(e->err, sizeof(int32_t));
     if (!rc) rc = e->alloc(e->envc, sizeof(EnvConst));
-    if (!rc) rc = e->alloc(e->goal, n * sizeof(uint32_t));
-    if (!rc) rc = e->alloc(e->predraw, n * sizeof(uint4));
+    if (!rc) rc = e->alloc(e->goal, n * ap.goal);
+    if (!rc) rc = e->alloc(e->predraw, n * ap.predraw);
     if (!rc && l.pcache) rc = e->alloc(e->wimg, nr * VN_WIMG_REP * l.map_bytes);
-    if (!rc && l.pcache == 2) rc = e->alloc(e->stood, n * 34u * sizeof(uint32_t));
+    if (!rc && ap.stood) rc = e->alloc(e->stood, n * ((size_t)ap.stood + ap.pnz));
     if (!rc) rc = e->alloc(e->scratch, 8192);
     // after every other buffer: none of them moves (allocation placement alone swings the rate)
-    if (!rc) rc = e->alloc(e->episodes, n * (size_t)l.episode_bytes);
+    if (!rc) rc = e->alloc(e->episodes, n * (size_t)ap.episode);
     return rc;
 }
 
@@ -274,21 +279,23 @@ struct SnapPart {
 
 // hot state with the window records behind it, next seeds, belief blocks,
 // goals, the simpleEnv draw-ahead, the episode records, stood rows with the
-// nonzero-set masks
+// nonzero-set masks; N rows each of the size agent_parts plans (env_plan.h:
+// snapshot_bytes lays the blob out in this order, each part on a SNAP_ALIGN
+// boundary)
 constexpr int SNAP_MAX_PARTS = 7;
 int snap_parts(const VnEnv *e, SnapPart out[SNAP_MAX_PARTS]) {
+    const AgentParts ap = agent_parts(e->lay);
+    const size_t N = (size_t)e->N;
     int n = 0;
-    out[n++] = {e->hot.ptr, e->hot.bytes};
-    out[n++] = {e->seed.ptr, e->seed.bytes};
-    out[n++] = {e->params.belief, (size_t)e->lay.agent_bytes * (size_t)e->N};
-    out[n++] = {e->goal.ptr, e->goal.bytes};
-    out[n++] = {e->predraw.ptr, e->predraw.bytes};
-    out[n++] = {e->episodes.ptr, e->episodes.bytes};
-    if (e->stood.ptr) out[n++] = {e->stood.ptr, e->stood.bytes};
+    out[n++] = {e->hot.ptr, N * ((size_t)ap.hot + ap.wrec)};
+    out[n++] = {e->seed.ptr, N * ap.seed};
+    out[n++] = {e->params.belief, N * ap.belief};
+    out[n++] = {e->goal.ptr, N * ap.goal};
+    out[n++] = {e->predraw.ptr, N * ap.predraw};
+    out[n++] = {e->episodes.ptr, N * ap.episode};
+    if (ap.stood) out[n++] = {e->stood.ptr, N * ((size_t)ap.stood + ap.pnz)};
     return n;
 }
-
-constexpr size_t SNAP_ALIGN = 256;   // each part starts on a 256-byte boundary of the blob
 
 // FNV-1a over the values that decide the bytes' meaning: ABI version, variant,
 // N, L, the planned layout, the creation-time tuning, the config and the room
@@ -303,18 +310,20 @@ struct Fnv {
     void val(T v) { bytes(&v, sizeof(v)); }
 };
 
-uint64_t snapshot_tag(const VnEnv *e, const RoomTables &rt) {
+// whole_env false: the layout tag -- what decides one agent's bytes, i.e. the
+// same list without N, agent_id_base and the episode buffer's size
+uint64_t snapshot_tag(const VnEnv *e, const RoomTables &rt, bool whole_env) {
     const EnvLayout &l = e->lay;
     Fnv f;
     f.val<int32_t>(VN_ABI_VERSION);
     f.val<int32_t>(l.variant);
-    f.val<int32_t>(e->N);
+    if (whole_env) f.val<int32_t>(e->N);
     f.val<int32_t>(e->cfg.local_map_length);
     for (const int32_t v : {l.obs_dim, l.pw, l.pd, l.ph, l.nbx, l.nby, l.nwx, l.nwy, l.sbits, l.sline, l.defer, l.pcache})
         f.val<int32_t>(v);
     for (const uint32_t v : {l.map_bytes, l.agent_bytes, l.plane_bytes, l.xp_off, l.yp_off, l.sy_off, l.sz_off, l.qz_off})
         f.val<uint32_t>(v);
-    f.val<uint64_t>((uint64_t)e->episodes.bytes);   // the episode records travel with a snapshot
+    if (whole_env) f.val<uint64_t>((uint64_t)e->episodes.bytes);   // the episode records travel with a snapshot
     f.val<int32_t>(e->tuning.pcache_cap);
     f.val<int32_t>(e->tuning.defer);
     f.val<int32_t>(e->tuning.simple_layout);
@@ -322,7 +331,7 @@ uint64_t snapshot_tag(const VnEnv *e, const RoomTables &rt) {
     f.val<int32_t>(e->cfg.autoreset);
     f.val<double>(e->cfg.crash_penalty);
     f.val<double>(e->cfg.finish_percentage);
-    f.val<int64_t>(e->cfg.agent_id_base);
+    if (whole_env) f.val<int64_t>(e->cfg.agent_id_base);
     f.val<int64_t>(e->cfg.seed_stride);
     f.bytes(rt.desc.data(), rt.desc.size() * sizeof(uint32_t));
     f.bytes(rt.rays.data(), rt.rays.size() * sizeof(RayRec));
@@ -433,7 +442,8 @@ int vn_create_tuned(const VnRoomSet *rooms, int32_t n_agents, const VnConfig *cf
     const size_t belief_bytes = (size_t)e->lay.agent_bytes * (size_t)n_agents;
     if (const int rc = alloc_buffers(e.get(), rt, belief_bytes + belief_off, belief_contig)) return rc;
     e->params = env_params(e.get(), belief_off);
-    e->snap_tag = snapshot_tag(e.get(), rt);
+    e->snap_tag = snapshot_tag(e.get(), rt, true);
+    e->layout_tag = snapshot_tag(e.get(), rt, false);
     if (const hipError_t he = upload(e.get(), *rooms, rt, lut))
         return fail(VN_ERR_HIP, "vn_create upload: %s", hipGetErrorString(he));
     *out = e.release();
@@ -499,6 +509,24 @@ int vn_step_random(VnEnv *env, uint64_t policy_seed, uint64_t t0, int32_t k_step
     p.policy_seed = policy_seed;
     p.t0 = t0;
     p.actions_out = actions_out;
+    p.obs = obs;
+    p.reward = reward;
+    p.reward64 = reward64;
+    p.term = terminated;
+    p.trunc = truncated;
+    p.terminal_obs = terminal_obs;
+    return launch_env(false, env, p, (hipStream_t)stream);
+}
+
+int vn_step_actions(VnEnv *env, const int32_t *actions, int32_t k_steps, float *obs, float *reward, double *reward64,
+                    uint8_t *terminated, uint8_t *truncated, float *terminal_obs, void *stream) {
+    if (!env || !actions || !obs) return fail(VN_ERR_INVALID, "NULL argument");
+    if (k_steps < 1) return fail(VN_ERR_INVALID, "k_steps must be >= 1 (got %d)", k_steps);
+    DeviceGuard dg(env->device);
+    Params p = call_params(env);
+    p.K = k_steps;      // vn_step's launch with k_steps steps in it: actions [k_steps][N], t0 = 0
+    p.t0 = 0;
+    p.actions = actions;
     p.obs = obs;
     p.reward = reward;
     p.reward64 = reward64;
@@ -579,11 +607,7 @@ int vn_snapshot_tag(const VnEnv *env, uint64_t *tag) {
 
 int vn_snapshot_bytes(const VnEnv *env, int64_t *bytes) {
     if (!env || !bytes) return fail(VN_ERR_INVALID, "NULL argument");
-    SnapPart parts[SNAP_MAX_PARTS];
-    const int n = snap_parts(env, parts);
-    size_t total = 0;
-    for (int k = 0; k < n; ++k) total += (parts[k].bytes + SNAP_ALIGN - 1) & ~(SNAP_ALIGN - 1);
-    *bytes = (int64_t)total;
+    *bytes = (int64_t)snapshot_bytes(agent_parts(env->lay), (size_t)env->N);
     return VN_OK;
 }
 
@@ -595,7 +619,7 @@ int vn_snapshot_save(VnEnv *env, void *dst, void *stream) {
     char *d = static_cast<char *>(dst);
     for (int k = 0; k < n; ++k) {
         VN_HIP(hipMemcpyAsync(d, parts[k].ptr, parts[k].bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-        d += (parts[k].bytes + SNAP_ALIGN - 1) & ~(SNAP_ALIGN - 1);
+        d += snap_up(parts[k].bytes);
     }
     return VN_OK;
 }
@@ -612,12 +636,31 @@ int vn_snapshot_load(VnEnv *env, const void *src, uint64_t tag, void *stream) {
     const char *s = static_cast<const char *>(src);
     for (int k = 0; k < n; ++k) {
         VN_HIP(hipMemcpyAsync(parts[k].ptr, s, parts[k].bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-        s += (parts[k].bytes + SNAP_ALIGN - 1) & ~(SNAP_ALIGN - 1);
+        s += snap_up(parts[k].bytes);
     }
     // the copied hot words carry their window-record bits and the records came
     // with them, so the next launch reads each record after its state
     env->wrec_written = false;
     return VN_OK;
+}
+
+int vn_copy_agents(VnEnv *dst, const VnEnv *src, const int32_t *src_index, const int64_t *seeds, int32_t *n_rejected,
+                   void *stream) {
+    if (!dst || !src || !src_index) return fail(VN_ERR_INVALID, "NULL argument");
+    if (dst->device != src->device)
+        return fail(VN_ERR_INVALID, "vn_copy_agents: the envs are on devices %d and %d (no cross-device copy)",
+                    dst->device, src->device);
+    if (dst->layout_tag != src->layout_tag)
+        return fail(VN_ERR_INVALID, "vn_copy_agents: the envs' layout tags differ (%016llx, %016llx): another variant, "
+                                    "local_map_length, layout, creation-time tuning, config or room set",
+                    (unsigned long long)dst->layout_tag, (unsigned long long)src->layout_tag);
+    DeviceGuard dg(dst->device);
+    const Params pd = call_params(dst), ps = call_params(src);
+    // a copied hot word keeps its window-record bit and the record came with
+    // it: the next launch reads each record after its state (vn_snapshot_load)
+    dst->wrec_written = false;
+    const AgentParts ap = agent_parts(dst->lay);
+    return vn_gather::copy_agents(&pd, &ps, &ap, src_index, seeds, n_rejected, (hipStream_t)stream);
 }
 
 #ifdef VN_DIAG

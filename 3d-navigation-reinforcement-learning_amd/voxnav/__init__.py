@@ -16,6 +16,7 @@ include/voxnav.h.  Public API:
   evaluate_policy     evaluate_grid.py's deterministic-episode metrics, batched
   save_checkpoint / load_checkpoint   SB3 .zip layout, Grid_Train naming
   checkpoint.save_env_state / load_env_state   an env's agents (.npz: portable exports or a raw snapshot)
+  branch.fan_out / branch.evaluate_plans   copies of chosen agents in a wider env; the returns of K-step action plans
   sharding            multi-GPU agent sharding helpers
 """
 from . import rooms  # noqa: F401

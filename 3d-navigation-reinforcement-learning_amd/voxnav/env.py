@@ -46,6 +46,7 @@ class Rollout(NamedTuple):
     terminated: torch.Tensor     # bool [K, N]
     truncated: torch.Tensor      # bool [K, N]
     actions: Optional[torch.Tensor]  # i32 [K, N]
+    terminal_obs: Optional[torch.Tensor] = None  # f32 [K, N, obs_dim] (step_actions): rows valid where an episode ended
 
 
 class EnvSnapshot(NamedTuple):
@@ -277,18 +278,94 @@ class BatchedGridEnv:
             act = torch.empty((K, N), dtype=torch.int32, device=self.device) if record_actions else None
         else:
             self._check_rollout(out, K, reward_f64)
-            obs, rew, te, tr, act = out
+            obs, rew, te, tr, act = out[:5]
         _native.check(self.lib.vn_step_random(self._h, int(policy_seed), int(t0), K, _ptr(act), _ptr(obs),
                                               None if reward_f64 else _ptr(rew), _ptr(rew) if reward_f64 else None,
                                               _ptr(te), _ptr(tr), None, self._stream()), "vn_step_random")
         self._t = int(t0) + K
         return Rollout(obs, rew, te, tr, act)
 
+    def step_actions(self, actions, reward_f64: bool = False, terminal_obs: bool = False,
+                     out: Optional[Rollout] = None, reward64: Optional[torch.Tensor] = None) -> Rollout:
+        """K fused steps of given actions (``vn_step_actions``): ``step``'s
+        semantics per step, auto-reset included, ``step_random``'s [K, N, ...]
+        output layout, one launch.  ``actions`` is int [K, N]; it comes back
+        (as the int32 device tensor the kernel read) in ``Rollout.actions``.
+        ``terminal_obs=True`` adds ``Rollout.terminal_obs`` [K, N, obs_dim],
+        whose row [k, i] is written (else zero) where agent i's step k ended
+        an episode.  ``reward64`` (f64 [K, N], next to an f32 reward) also
+        receives the exact f64 rewards, as in ``step_into``.  The random
+        policy's step counter advances by K."""
+        if not self._was_reset:
+            raise RuntimeError("call reset() before step_actions()")
+        N = self.num_agents
+        a = torch.as_tensor(actions, device=self.device).to(torch.int32)
+        if a.dim() != 2 or a.shape[1] != N or a.shape[0] < 1:
+            raise ValueError(f"actions: expected [K, {N}] with K >= 1, got {tuple(a.shape)}")
+        a = a.contiguous()
+        K = int(a.shape[0])
+        if out is None:
+            obs = torch.empty((K, N, self.obs_dim), dtype=torch.float32, device=self.device)
+            rew = torch.empty((K, N), dtype=torch.float64 if reward_f64 else torch.float32, device=self.device)
+            te = torch.empty((K, N), dtype=torch.uint8, device=self.device)
+            tr = torch.empty((K, N), dtype=torch.uint8, device=self.device)
+            tob = None
+        else:
+            self._check_rollout(out, K, reward_f64)
+            obs, rew, te, tr = out[:4]
+            tob = out.terminal_obs
+            if tob is not None and (tob.dtype != torch.float32 or tuple(tob.shape) != (K, N, self.obs_dim)
+                                    or not tob.is_contiguous() or tob.device != self.device):
+                raise ValueError(f"out.terminal_obs: expected contiguous float32 {(K, N, self.obs_dim)} on {self.device}")
+        if terminal_obs and tob is None:
+            tob = torch.zeros((K, N, self.obs_dim), dtype=torch.float32, device=self.device)
+        if reward64 is not None and (reward_f64 or reward64.dtype != torch.float64 or tuple(reward64.shape) != (K, N)
+                                     or not reward64.is_contiguous() or reward64.device != self.device):
+            raise ValueError(f"reward64: expected contiguous f64 {(K, N)} on {self.device} next to an f32 reward")
+        _native.check(self.lib.vn_step_actions(self._h, _ptr(a), K, _ptr(obs), None if reward_f64 else _ptr(rew),
+                                               _ptr(rew) if reward_f64 else _ptr(reward64), _ptr(te), _ptr(tr), _ptr(tob),
+                                               self._stream()), "vn_step_actions")
+        self._t += K
+        return Rollout(obs, rew, te, tr, a, tob)
+
+    def copy_agents(self, src_env: "BatchedGridEnv", src_index, seeds=None) -> torch.Tensor:
+        """Agent i of this env becomes a layout-native copy of agent
+        ``src_index[i]`` of ``src_env`` (-1: i keeps its state;
+        ``vn_copy_agents``).  ``src_env`` may be this env, or any env on the
+        same device built alike but for ``num_agents`` and ``agent_id_base``
+        (same variant, rooms, config, ``seed_stride`` and creation-time
+        tuning); both must have been reset.  ``seeds`` (int64 [N], optional):
+        ``seeds[i] >= 0`` replaces the copied next auto-reset seed, -1 keeps
+        the source's.  The episode records stay with the slots.  Returns the
+        device int32 [1] count of destinations the device-side validation
+        rejected and left untouched (an index or seed out of range; in place,
+        a source that the same call writes); no host sync."""
+        if not isinstance(src_env, BatchedGridEnv):
+            raise TypeError("src_env must be a BatchedGridEnv")
+        if not (self._was_reset and src_env._was_reset):
+            raise RuntimeError("copy_agents() needs both envs reset (or imported / restored) before")
+        if src_env.device != self.device:
+            raise ValueError(f"src_env is on {src_env.device}, this env on {self.device}")
+        N = self.num_agents
+        idx = torch.as_tensor(src_index, device=self.device).to(torch.int32).reshape(-1).contiguous()
+        if idx.numel() != N:
+            raise ValueError(f"src_index: expected {N} entries, got {idx.numel()}")
+        sd = None
+        if seeds is not None:
+            sd = torch.as_tensor(seeds, device=self.device).to(torch.int64).reshape(-1).contiguous()
+            if sd.numel() != N:
+                raise ValueError(f"seeds: expected {N} entries, got {sd.numel()}")
+        rej = torch.zeros(1, dtype=torch.int32, device=self.device)
+        _native.check(self.lib.vn_copy_agents(self._h, src_env._h, _ptr(idx), _ptr(sd), _ptr(rej), self._stream()),
+                      "vn_copy_agents")
+        self._was_reset = True
+        return rej
+
     def _check_rollout(self, out: Rollout, K: int, reward_f64: bool):
         """A caller-owned [K, N, ...] rollout chunk: the kernel writes all K
         steps, so a short or mistyped buffer is refused here."""
         N, dev = self.num_agents, self.device
-        obs, rew, te, tr, act = out
+        obs, rew, te, tr, act = out[:5]
         rdt = torch.float64 if reward_f64 else torch.float32
         for name, t, dt, shape in (("obs", obs, torch.float32, (K, N, self.obs_dim)), ("reward", rew, rdt, (K, N)),
                                    ("terminated", te, torch.uint8, (K, N)), ("truncated", tr, torch.uint8, (K, N))):
@@ -307,7 +384,7 @@ class BatchedGridEnv:
             raise RuntimeError("call reset() before step_random()")
         K = int(k_steps)
         self._check_rollout(out, K, reward_f64)
-        obs, rew, te, tr, act = out
+        obs, rew, te, tr, act = out[:5]
         args = (self._h, int(policy_seed), int(t0), K, _ptr(act), _ptr(obs), None if reward_f64 else _ptr(rew),
                 _ptr(rew) if reward_f64 else None, _ptr(te), _ptr(tr), None, self._stream())
         fn = self.lib.vn_step_random

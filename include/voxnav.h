@@ -189,6 +189,28 @@ int vn_step_random(VnEnv *env, uint64_t policy_seed, uint64_t t0, int32_t k_step
                    float *terminal_obs, void *stream);
 
 /*
+ * k_steps fused steps of caller-given actions: vn_step's semantics per step
+ * (auto-reset included), vn_step_random's output layout, one launch -- a
+ * recorded action log replayed, or an action plan evaluated, without a launch
+ * per step.
+ *   actions       device i32 [k_steps][N], each in 0..5
+ *   obs           device f32 [k_steps][N][obs_dim]
+ *   reward / reward64 / terminated / truncated
+ *                 device [k_steps][N] (each may be NULL, as in vn_step)
+ *   terminal_obs  device f32 [k_steps][N][obs_dim] (may be NULL): row [k][i] is
+ *                 written only where agent i's step k ended an episode
+ * The launch is the one vn_step makes, with k_steps steps in it: the same
+ * explicit-action kernels, and the window records are written by launches of at
+ * most VnTuning::wrec_k steps as for every other call.  k_steps one-step
+ * vn_step calls and one vn_step_actions(k_steps) call leave the same outputs
+ * and the same env.  VN_ERR_INVALID: k_steps < 1, NULL env / actions / obs.
+ * No reference counterpart (the reference steps one env at a time).
+ */
+int vn_step_actions(VnEnv *env, const int32_t *actions, int32_t k_steps, float *obs, float *reward,
+                    double *reward64, uint8_t *terminated, uint8_t *truncated, float *terminal_obs,
+                    void *stream);
+
+/*
  * Parity dumps.  state_out: device i64 [N][16] in the field order
  * x, y, z, facing, last_action, step_count, visited_count, bump_count,
  * done, last_bump, near_wall, was_near_wall, cells_insight_down, room,
@@ -282,6 +304,45 @@ int vn_snapshot_tag(const VnEnv *env, uint64_t *tag);
 int vn_snapshot_bytes(const VnEnv *env, int64_t *bytes);
 int vn_snapshot_save(VnEnv *env, void *dst, void *stream);
 int vn_snapshot_load(VnEnv *env, const void *src, uint64_t tag, void *stream);
+
+/*
+ * Per-agent copies between envs (both variants, every layout): agent i of dst
+ * becomes a layout-native copy of agent src_index[i] of src (-1: agent i keeps
+ * its state).  One launch, stream-ordered, no host synchronisation.
+ *   src_index   device i32 [N_dst]
+ *   seeds       device i64 [N_dst] or NULL: seeds[i] >= 0 replaces the copied
+ *               next auto-reset seed, -1 keeps the source's
+ *   n_rejected  device i32 [1] (may be NULL; zeroed by the call first)
+ * What is copied: the agent's block of every mutable per-agent buffer -- its
+ * hot word and (CubicEnv) the window record behind it, the next seed, the
+ * belief block, the goal, the simpleEnv draw-ahead row and (plane-set mode 2)
+ * the 32 stood rows and the nonzero-set mask.  The running episode's counters
+ * are part of the hot word and travel; the episode records (vn_episode_*)
+ * stay with the slot, as after vn_import_state.  The random policy of
+ * vn_step_random is keyed by the agent's slot, not by its state: a copy
+ * repeats its source only under explicit actions (vn_step, vn_step_actions).
+ * Afterwards dst's "the previous launch wrote every window record" flag is
+ * false, as after vn_snapshot_load: a copied hot word keeps its record bit and
+ * its record came with it.  A simpleEnv draw-ahead row is valid only for the
+ * seed it was drawn for, so a seed override leaves the copied row unused.
+ *
+ * The envs must be on one device and agree in everything vn_snapshot_tag
+ * hashes except N, agent_id_base and the size of the episode records (the
+ * "layout tag": variant, L, the planned layout, the creation-time tuning, the
+ * config, seed_stride included, and the room tables).  Otherwise VN_ERR_INVALID
+ * with the reason in vn_last_error(), and nothing is launched.
+ *
+ * Validation runs on the device before anything of an agent is written.  A
+ * rejected destination is left untouched and counted in *n_rejected:
+ *   src_index[i] < -1 or >= N_src; seeds[i] < -1 or >= 2^32;
+ *   dst == src (allowed) and the source j != i is itself written by this call:
+ *   src_index[j] is neither -1 nor j, or seeds[j] is not -1.
+ * With that rule an in-place fan-out needs no pre-pass: every decision is a
+ * function of src_index and seeds alone, and a block reads only agents that
+ * no block writes.  No reference counterpart.
+ */
+int vn_copy_agents(VnEnv *dst, const VnEnv *src, const int32_t *src_index, const int64_t *seeds,
+                   int32_t *n_rejected, void *stream);
 
 /*
  * Episode records (both variants): what the reference reports at every
