@@ -4,10 +4,70 @@
 // simpleEnv step kernels (line layout for rooms <= 32 x 32 x 8, word layout
 // up to 64 x 64 x 31, dense maps beyond), their reset kernel and belief
 // export, and the launcher voxnav_api.hip's launch_env calls (vn_simple).
+// Three headers that only this unit includes hold what the kernels are built
+// from: simple_draw.h (an episode's MT19937 draws), simple_bits.h (ray
+// directions, the bit-plane belief and its observes), simple_line.h (the line
+// layout's lane-pair loads and stores).  Here: the step pieces the kernels
+// share, the kernels, and pick(), the one place that maps a call shape to a
+// kernel for launch and label.
 
 #include "env_core.h"
 
+#include "simple_draw.h"
+#include "simple_bits.h"
+#include "simple_line.h"
+
 namespace {
+
+// ============================================================================
+// Step pieces shared by the simpleEnv kernels (dense, word and line layout).
+// ============================================================================
+
+// an agent at the start of the episode drawn = (start | room << 24, goal)
+__device__ __forceinline__ void reset_agent(const Params &p, uint2 drawn, Agent &g, uint32_t &goal, Room &R) {
+    g.room = (int)(drawn.x >> 24);
+    R = load_room(p, g.room);
+    g.x = drawn.x & 0xff;
+    g.y = (drawn.x >> 8) & 0xff;
+    g.z = (drawn.x >> 16) & 0xff;
+    goal = drawn.y;
+    g.facing = 0;
+    g.last_action = 0;
+    g.done = g.last_bump = g.near_wall = g.was_near_wall = false;
+    g.step_count = 0;
+    g.visited = 1;
+    g.bumps = 0;
+    g.cid = 0;
+    g.move_mask = 0;
+}
+
+// the wave zeroes the belief blocks of the agents in `m` (bits: lanes of the
+// block that starts at agent block_agent0): all of the block for those in
+// `mq`, up to QZ (its last part) for the others
+__device__ __forceinline__ void zero_agent_blocks(const Params &p, uint64_t m, uint64_t mq, int block_agent0, int lane) {
+    while (m) {
+        const int src = __ffsll((unsigned long long)m) - 1;
+        m &= m - 1;
+        const uint32_t n16 = (((mq >> src) & 1ull) ? p.agent_bytes : p.qz_off) >> 4;
+        uint4 *base = reinterpret_cast<uint4 *>(p.belief + (size_t)(block_agent0 + src) * p.agent_bytes);
+        for (uint32_t q = (uint32_t)lane; q < n16; q += 64u) base[q] = make_uint4(0u, 0u, 0u, 0u);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+}
+
+// an agent's state into registers (lanes past N: zeros) and back
+__device__ __forceinline__ void load_agent(const Params &p, int ai, bool live, Agent &g, uint32_t &goal,
+                                           uint32_t &next_seed, Room &R) {
+    g = unpack(live ? p.hot[ai] : make_uint4(0u, 0u, 0u, 0u));
+    goal = live ? p.goal[ai] : 0u;
+    next_seed = live ? p.next_seed[ai] : 0u;
+    R = load_room(p, g.room);
+}
+__device__ __forceinline__ void store_agent(const Params &p, int ai, const Agent &g, uint32_t goal, uint32_t next_seed) {
+    p.hot[ai] = pack(g);
+    p.goal[ai] = goal;
+    p.next_seed[ai] = next_seed;
+}
 
 // ============================================================================
 // simpleEnv variant (envs/simpleEnv.py): walls are
@@ -18,146 +78,6 @@ namespace {
 // (obs_dim = 6L + 7).  One lane per agent, 64 agents per block; obs rows are
 // staged in LDS and written as one contiguous span per block.
 // ============================================================================
-
-// absolute ray directions of the relative moves (envs/simpleEnv.py:153-158,
-// :224-231) in the ray-record byte order 0:+x 1:-x 2:+y 3:-y 4:+z 5:-z
-constexpr int kRelDir[4][4] = {
-    {2, 0, 3, 1},   // forward  (N, E, S, W)
-    {0, 3, 1, 2},   // right
-    {3, 1, 2, 0},   // backward
-    {1, 2, 0, 3},   // left
-};
-constexpr uint32_t pack_rel_dir() {
-    uint32_t v = 0;
-    for (int a = 0; a < 4; ++a)
-        for (int f = 0; f < 4; ++f) v |= (uint32_t)kRelDir[a][f] << (2 * (4 * a + f));
-    return v;
-}
-// 2-bit fields in one immediate: no memory lookups on the step's critical path
-__device__ __forceinline__ int rel_dir(int a, int facing) {
-    return (int)((pack_rel_dir() >> (2 * (4 * a + facing))) & 3u);
-}
-// +x -> east(1), -x -> west(3), +y -> north(0), -y -> south(2)
-__device__ __forceinline__ int facing_of(int d) { return (int)((0x8Du >> (2 * d)) & 3u); }
-
-// obs slot of absolute direction j < 4 for facing f: slot k with rel_dir of
-// [fwd, left, right, back][k] == j
-constexpr uint32_t pack_obs_slot() {
-    uint32_t v = 0;
-    const int rel_of_slot[4] = {0, 3, 1, 2};   // forward, left, right, backward (action indices)
-    for (int f = 0; f < 4; ++f)
-        for (int k = 0; k < 4; ++k) v |= (uint32_t)k << (2 * (4 * f + kRelDir[rel_of_slot[k]][f]));
-    return v;
-}
-__device__ __forceinline__ int obs_slot(int j, int facing) {
-    return j >= 4 ? j : (int)((pack_obs_slot() >> (2 * (4 * facing + j))) & 3u);
-}
-
-
-// MT draws of simpleEnv's load_room (:350, :410-426): room, start (drawn if
-// absent or on a wall), goal (drawn if absent or on a wall).  Returns
-// (start | room<<24, goal).
-template <bool INL>
-__device__ __attribute__((always_inline)) inline uint2 simple_draw_t(const EnvConst *ec, uint32_t seed);
-template <typename MT>
-__device__ __attribute__((always_inline)) inline uint2 simple_draw_from(const EnvConst *ec, MT &mt);
-__device__ __noinline__ uint2 simple_draw(const EnvConst *ec, uint32_t seed) { return simple_draw_t<false>(ec, seed); }
-template <bool INL>
-__device__ __attribute__((always_inline)) inline uint2 simple_draw_t(const EnvConst *ec, uint32_t seed) {
-    MtStreamT<INL> mt;
-    mt.seed = seed;
-    mt.used = 0;
-    mt.err = ec->err;
-    if constexpr (INL) {
-        const MtBlock b0 = mt_outputs_inl(seed, 0);
-#pragma unroll
-        for (int j = 0; j < MT_C; ++j) mt.buf[j] = b0.w[j];
-    } else {
-        mt_first_outputs(seed, mt.buf);
-    }
-    return simple_draw_from(ec, mt);
-}
-
-// The first MT_W = 24 outputs of random.seed(seed) in ONE pass of the two
-// init_by_array chains (mt_outputs captures 8 per pass; a wave-wide draw of
-// 64 lanes would otherwise re-run the chains whenever any lane's rejection
-// sampling passed 8 outputs), written to the lane's LDS row (stride MT_WS).
-constexpr int MT_W = 24, MT_WS = 25;
-__device__ __noinline__ void mt_outputs_wide(uint32_t seed, uint32_t *lds_row) {
-    uint32_t p = mix1(c_mt_g[1], c_mt_g[0], seed);
-    const uint32_t m1_1 = p;
-    p = mt_loop1(p, seed);
-    const uint32_t m1b1 = mix1(m1_1, p, seed);   // wrap: i = 1 again, mt[0] = mt[623]
-    uint32_t p1 = m1_1, q = m1b1;
-    uint32_t lo[MT_W + 1], hi[MT_W];             // F[0 .. MT_W], F[397 .. 397 + MT_W - 1]
-#pragma unroll
-    for (int i = 2; i <= MT_W; ++i) {
-        p1 = mix1(c_mt_g[i], p1, seed);
-        q = mix2(p1, q, (uint32_t)i);
-        lo[i] = q;
-    }
-    mt_loop2(p1, q, MT_W + 1, 397, seed);
-#pragma unroll
-    for (int k = 0; k < MT_W; ++k) {
-        const int i = 397 + k;
-        p1 = mix1(c_mt_g[i], p1, seed);
-        q = mix2(p1, q, (uint32_t)i);
-        hi[k] = q;
-    }
-    mt_loop2(p1, q, 397 + MT_W, MT_N, seed);
-    lo[1] = mix2(m1b1, q, 1u);                   // F[1]: loop 2's wrap step
-    lo[0] = 0x80000000u;                         // F[0]
-#pragma unroll
-    for (int j = 0; j < MT_W; ++j) {
-        const uint32_t y = (lo[j] & 0x80000000u) | (lo[j + 1] & 0x7fffffffu);
-        lds_row[j] = mt_temper(hi[j] ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u));
-    }
-}
-
-// MT output stream over a lane's LDS row of MT_W outputs (mt_outputs_wide),
-// blocks past it recomputed one at a time (mt_refill)
-struct MtLdsStream {
-    const uint32_t *row;
-    uint32_t seed;
-    int used;
-    int32_t *err;
-    MtBlock ext;
-    __device__ uint32_t next() {
-        uint32_t r;
-        if (used < MT_W) {
-            r = row[used];
-        } else {
-            if ((used % MT_C) == 0) ext = mt_refill(seed, used, err);
-            const int j = used % MT_C;
-            r = ext.w[0];
-#pragma unroll
-            for (int t = 1; t < MT_C; ++t) r = j == t ? ext.w[t] : r;
-        }
-        ++used;
-        return r;
-    }
-    __device__ uint32_t below(uint32_t n) {
-        const int k = 32 - __clz(n);
-        uint32_t r = next() >> (32 - k);
-        while (r >= n) r = next() >> (32 - k);
-        return r;
-    }
-};
-
-template <typename MT>
-__device__ __attribute__((always_inline)) inline uint2 simple_draw_from(const EnvConst *ec, MT &mt) {
-    const int room = ec->use_room_draw ? (int)mt.below((uint32_t)ec->n_rooms) : 0;
-    const Room R = load_room_c(ec, room);
-    auto is_wall = [&](uint32_t c) {
-        const int x = c & 0xff, y = (c >> 8) & 0xff, z = (c >> 16) & 0xff;
-        return ((ec->rays[R.ray_off + (uint32_t)((x * R.D + y) * R.H + z)].y >> 16) & 1u) != 0u;
-    };
-    uint32_t s = R.fixed_start >= 0 ? (uint32_t)R.fixed_start : ec->starts[R.start_off + mt.below(R.total_free)];
-    if (is_wall(s)) s = ec->starts[R.start_off + mt.below(R.total_free)];
-    uint32_t gl = R.fixed_goal >= 0 ? (uint32_t)R.fixed_goal : ec->starts[R.start_off + mt.below(R.total_free)];
-    if (is_wall(gl)) gl = ec->starts[R.start_off + mt.below(R.total_free)];
-    return make_uint2((s & 0xffffffu) | ((uint32_t)room << 24), gl & 0xffffffu);
-}
 
 // _sense_direction (:301-337) along absolute direction d from the agent's
 // cell, using the cell's ray record (free run n to the first wall / edge).
@@ -221,20 +141,7 @@ __device__ void simple_reset_wave(const Params &p, int8_t *map, bool need, uint3
     }
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     if (need) {
-        g.room = (int)(drawn.x >> 24);
-        R = load_room(p, g.room);
-        g.x = drawn.x & 0xff;
-        g.y = (drawn.x >> 8) & 0xff;
-        g.z = (drawn.x >> 16) & 0xff;
-        goal = drawn.y;
-        g.facing = 0;
-        g.last_action = 0;
-        g.done = g.last_bump = g.near_wall = g.was_near_wall = false;
-        g.step_count = 0;
-        g.visited = 1;
-        g.bumps = 0;
-        g.cid = 0;
-        g.move_mask = 0;
+        reset_agent(p, drawn, g, goal, R);
         map[(g.x * p.pd + g.y) * p.ph + g.z] = 1;                              // :86
         simple_observe(map, p, g, R, row);
     }
@@ -247,14 +154,14 @@ __global__ __launch_bounds__(64) void simple_kernel(Params p) {
     const int a0 = blockIdx.x * 64;
     const int ai = a0 + lane;
     const bool live = ai < p.N;
-    const int OD = p.obs_dim, L = p.L;
+    const int OD = p.obs_dim;
     const int rows = min(64, p.N - a0);
     float *row = sstage + lane * OD;
     int8_t *map = p.belief + (size_t)(live ? ai : a0) * p.agent_bytes;
-    Agent g = unpack(live ? p.hot[ai] : make_uint4(0u, 0u, 0u, 0u));
-    uint32_t goal = live ? p.goal[ai] : 0u;
-    uint32_t next_seed = live ? p.next_seed[ai] : 0u;
-    Room R = load_room(p, g.room);
+    Agent g;
+    uint32_t goal, next_seed;
+    Room R;
+    load_agent(p, ai, live, g, goal, next_seed, R);
 
     if (RESET_ONLY) {
         const bool need = live && (!p.mask || p.mask[ai]);
@@ -354,227 +261,7 @@ __global__ __launch_bounds__(64) void simple_kernel(Params p) {
         for (int q = lane; q < rows * OD; q += 64) dst[q] = sstage[q];
         __syncthreads();
     }
-    if (live) {
-        p.hot[ai] = pack(g);
-        p.goal[ai] = goal;
-        p.next_seed[ai] = next_seed;
-    }
-    (void)L;
-}
-
-// ============================================================================
-// simpleEnv, bit-plane layout (rooms up to 64 x 64 x 31; larger rooms use the
-// dense kernel above).  The belief map is not stored as bytes.  Per agent:
-//   S  the agent has stood on the cell: internal_grid == 1 (:86, :294), or a
-//      visited cell the edge quirk later turned into 2.  Kept in three axis
-//      planes so that a ray along any axis is one word:
-//      SX[y][z] (bit x, u64), SY[x][z] (bit y, u64), SZ[x][y] (bit z, u32)
-//   Q  edge-quirk mark: the last in-room cell of a ray that leaves the room
-//      becomes 2 (:311-319).  QZ[x][y] (bit z, u32); agent flag in hot.w
-// Every other internal_grid value is a function of S, Q and the walls: the
-// positions the agent has sensed from are exactly its S cells (reset and
-// every step observe where the agent stands, and every such cell is marked),
-// so a cell is known -- 0 if free, 2 if wall -- iff an S cell lies within L
-// cells of it along an axis with only free cells in between (:301-337).
-// export_belief derives the map; the step reads only S and Q.  In-run obs
-// values: Q ? 2 : S ? 1 : 0.
-// ============================================================================
-struct SPlanes {
-    uint64_t *sx, *sy;
-    uint32_t *sz, *qz;
-};
-
-__device__ __forceinline__ SPlanes splanes(const Params &p, int agent) {
-    int8_t *b = p.belief + (size_t)agent * p.agent_bytes;
-    SPlanes q;
-    q.sx = reinterpret_cast<uint64_t *>(b);
-    q.sy = reinterpret_cast<uint64_t *>(b + p.sy_off);
-    q.sz = reinterpret_cast<uint32_t *>(b + p.sz_off);
-    q.qz = reinterpret_cast<uint32_t *>(b + p.qz_off);
-    return q;
-}
-
-// cached S words through the agent's cell + the cell's ray record
-struct SRows {
-    uint64_t wx, wy;
-    uint32_t wz;
-    uint2 rec;
-};
-
-__device__ __forceinline__ uint32_t ray_e8(uint2 rec, int d) {
-    return ((d < 4 ? rec.x : rec.y) >> (8 * (d & 3))) & 0xffu;
-}
-
-// simple_ray on the bit planes: obs values of ray d (L floats) from the S
-// word along the ray axis, Q bits looked up only when the agent has any;
-// then the edge-quirk mark.  Returns count * 0.25.
-// (scalars by value: a select over struct fields folds into a dynamic load
-// from a stack copy of the struct)
-template <int LMAX>
-__device__ __forceinline__ float sb_ray(const Params &p, const SPlanes &pl, int gx, int gy, int gz, bool hasq,
-                                        uint64_t wx, uint64_t wy, uint32_t wz, uint2 rec, int d, float *out,
-                                        bool &newq) {
-    const uint32_t e8 = ray_e8(rec, d);
-    const int n = (int)(e8 & 0x7fu);
-    const int L = p.L;
-    const int m = n < L ? n : L;
-    const int ax = d >> 1;
-    const int sgn = (d & 1) ? -1 : 1;
-    const uint64_t run = ax == 0 ? wx : ax == 1 ? wy : (uint64_t)wz;
-    const int pos = ax == 0 ? gx : ax == 1 ? gy : gz;
-#pragma unroll
-    for (int s = 0; s < LMAX; ++s) {
-        if (s >= L) break;
-        float v;
-        if (s < m) {
-            const int c = pos + sgn * (s + 1);
-            uint32_t b = (uint32_t)(run >> c) & 1u;
-            if (hasq) {
-                const int qx = ax == 0 ? c : gx, qy = ax == 1 ? c : gy, qzz = ax == 2 ? c : gz;
-                if ((pl.qz[qx * p.pd + qy] >> qzz) & 1u) b = 2u;
-            }
-            v = (float)b;
-        } else {
-            v = s == n ? 2.0f : -1.0f;   // wall / edge terminator, then padding (:321-331)
-        }
-        out[s] = v;
-    }
-    if (n < L && !(e8 & 0x80u) && n >= 1) {   // edge quirk (:311-319)
-        const int c = pos + sgn * n;
-        const int qx = ax == 0 ? c : gx, qy = ax == 1 ? c : gy, qzz = ax == 2 ? c : gz;
-        uint32_t *q = pl.qz + qx * p.pd + qy;
-        // no Q bit anywhere yet -> the word is 0 (up and down share a column)
-        const uint32_t old = (hasq || newq) ? *q : 0u;
-        if (!((old >> qzz) & 1u)) *q = old | (1u << qzz);
-        newq = true;
-    }
-    return (float)m * 0.25f;                 // round(count * 0.25, 2) is exact
-}
-
-template <int LMAX>
-__device__ __forceinline__ void sb_observe(const Params &p, const SPlanes &pl, Agent &g, const SRows &w, float *row) {
-    const int L = p.L;
-    const bool hasq = g.move_mask & 1u;
-    bool newq = false;
-    const int dirs[6] = {rel_dir(0, g.facing), rel_dir(3, g.facing), rel_dir(1, g.facing),
-                         rel_dir(2, g.facing), 4, 5};   // forward, left, right, backward, up, down (:233)
-#pragma unroll
-    for (int k = 0; k < 6; ++k)
-        row[6 * L + k] = sb_ray<LMAX>(p, pl, g.x, g.y, g.z, hasq, w.wx, w.wy, w.wz, w.rec, dirs[k], row + k * L, newq);
-    row[6 * L + 6] = (float)g.last_action;
-    if (newq) g.move_mask |= 1u;
-}
-
-// sb_observe without divergent branches, for waves in which no lane has Q
-// marks or stands where a ray ends at the room's edge (ray record bit 17):
-// the rays in ABSOLUTE directions (ray axis, sign and S word fixed per ray),
-// each written at the obs slot the agent's facing gives it (obs_slot).  Per
-// ray cell s < L: the S bit if s < min(n, L), else 2 at s == n (wall), else -1
-// (:301-337).  Otherwise the wave takes sb_observe.
-template <int LMAX>
-__device__ __forceinline__ void sp_observe(const Params &p, const SPlanes &pl, Agent &g, const SRows &w, float *row) {
-    const bool slow = (g.move_mask & 1u) || ((w.rec.y >> 17) & 1u);
-    if (__builtin_expect(__ballot(slow) != 0ull, 0)) {
-        sb_observe<LMAX>(p, pl, g, w, row);
-        return;
-    }
-    const int L = p.L;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        const uint32_t e8 = ray_e8(w.rec, j);
-        const int n = (int)(e8 & 0x7fu);
-        const int m = n < L ? n : L;
-        // t: bit s = the S bit of ray cell s + 1
-        uint32_t t;
-        if (j == 0) t = (uint32_t)(w.wx >> ((g.x + 1) & 63));
-        else if (j == 2) t = (uint32_t)(w.wy >> ((g.y + 1) & 63));
-        else if (j == 4) t = w.wz >> ((g.z + 1) & 31);
-        else if (j == 1) t = __builtin_bitreverse32((uint32_t)((w.wx << ((64 - g.x) & 63)) >> 32));
-        else if (j == 3) t = __builtin_bitreverse32((uint32_t)((w.wy << ((64 - g.y) & 63)) >> 32));
-        else t = __builtin_bitreverse32(w.wz << ((32 - g.z) & 31));
-        float *out = row + obs_slot(j, g.facing) * L;
-#pragma unroll
-        for (int s = 0; s < LMAX; ++s) {
-            if (s >= L) break;
-            const float fb = ((t >> s) & 1u) ? 1.0f : 0.0f;
-            const float pad = s == n ? 2.0f : -1.0f;
-            out[s] = s < m ? fb : pad;
-        }
-        row[6 * L + obs_slot(j, g.facing)] = (float)m * 0.25f;   // round(count * 0.25, 2) is exact
-    }
-    row[6 * L + 6] = (float)g.last_action;
-}
-
-// Four ray cells at once: entry (bits | (clamp(m - 4c, -1, 4) + 1) << 4) of
-// the table holds the obs values of cells 4c..4c+3 of a ray with min(n, L) = m
-// free cells whose S bits (cells 4c..4c+3) are `bits`: the S bit below m, 2 at
-// m (the wall / edge terminator -- only reached when n < L), -1 beyond.
-constexpr int SL_CLUT = 96;
-__device__ __forceinline__ void sl_build_cell_lut(float4 *lut, int lane) {
-    for (int e = lane; e < SL_CLUT; e += 64) {
-        const int bits = e & 15, r = (e >> 4) - 1;
-        float v[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = i < r ? (float)((bits >> i) & 1) : (i == r ? 2.0f : -1.0f);
-        lut[e] = make_float4(v[0], v[1], v[2], v[3]);
-    }
-}
-
-// sp_observe with the 4-cell table, for L == LMAX (the ray cells of a launch
-// written without per-cell compares or branches)
-template <int LMAX>
-__device__ __forceinline__ void sl_observe(const Params &p, const SPlanes &pl, Agent &g, const SRows &w, float *row,
-                                           const float4 *clut) {
-    const bool slow = (g.move_mask & 1u) || ((w.rec.y >> 17) & 1u);
-    if (__builtin_expect(__ballot(slow) != 0ull || p.L != LMAX, 0)) {
-        sb_observe<LMAX>(p, pl, g, w, row);
-        return;
-    }
-    constexpr int L = LMAX;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-        const uint32_t e8 = ray_e8(w.rec, j);
-        const int n = (int)(e8 & 0x7fu);
-        const int m = n < L ? n : L;
-        uint32_t t;   // bit s = the S bit of ray cell s + 1
-        if (j == 0) t = (uint32_t)w.wx >> ((g.x + 1) & 31);
-        else if (j == 2) t = (uint32_t)w.wy >> ((g.y + 1) & 31);
-        else if (j == 4) t = w.wz >> ((g.z + 1) & 31);
-        else if (j == 1) t = __builtin_bitreverse32((uint32_t)w.wx << ((32 - g.x) & 31));
-        else if (j == 3) t = __builtin_bitreverse32((uint32_t)w.wy << ((32 - g.y) & 31));
-        else t = __builtin_bitreverse32(w.wz << ((32 - g.z) & 31));
-        const int slot = obs_slot(j, g.facing);
-        float *out = row + slot * L;
-#pragma unroll
-        for (int c = 0; c < (L + 3) / 4; ++c) {
-            const int r = min(max(m - 4 * c, -1), 4);
-            const float4 q = clut[((t >> (4 * c)) & 15u) | ((uint32_t)(r + 1) << 4)];
-            out[4 * c] = q.x;
-            if (4 * c + 1 < L) out[4 * c + 1] = q.y;
-            if (4 * c + 2 < L) out[4 * c + 2] = q.z;
-            if (4 * c + 3 < L) out[4 * c + 3] = q.w;
-        }
-        row[6 * L + slot] = (float)m * 0.25f;   // round(count * 0.25, 2) is exact
-    }
-    row[6 * L + 6] = (float)g.last_action;
-}
-
-__device__ __forceinline__ void sb_load_rows(const Params &p, const SPlanes &pl, const Agent &g, const Room &R,
-                                             SRows &w) {
-    w.wx = pl.sx[g.y * p.ph + g.z];
-    w.wy = pl.sy[g.x * p.ph + g.z];
-    w.wz = pl.sz[g.x * p.pd + g.y];
-    w.rec = p.rays[R.ray_off + (uint32_t)((g.x * R.D + g.y) * R.H + g.z)];
-}
-
-// after a move along axis ax the S word along that axis is the same row (only
-// this agent writes it, so the cached copy is current): reload the other two
-__device__ __forceinline__ void sb_move_rows(const Params &p, const SPlanes &pl, const Agent &g, const Room &R,
-                                             SRows &w, int ax) {
-    if (ax != 0) w.wx = pl.sx[g.y * p.ph + g.z];
-    if (ax != 1) w.wy = pl.sy[g.x * p.ph + g.z];
-    if (ax != 2) w.wz = pl.sz[g.x * p.pd + g.y];
-    w.rec = p.rays[R.ray_off + (uint32_t)((g.x * R.D + g.y) * R.H + g.z)];
+    if (live) store_agent(p, ai, g, goal, next_seed);
 }
 
 // reset for the lanes with `need` (as simple_reset_wave): the wave zeroes
@@ -584,30 +271,9 @@ __device__ __forceinline__ void sb_reset_wave(const Params &p, const SPlanes &pl
                               Room &R, SRows &w, float *row, int lane, int block_agent0) {
     uint2 drawn = make_uint2(0u, 0u);
     if (need) drawn = simple_draw(p.envc, seed);
-    uint64_t m = __ballot(need);
-    const uint32_t n16 = p.agent_bytes >> 4;
-    while (m) {
-        const int src = __ffsll((unsigned long long)m) - 1;
-        m &= m - 1;
-        uint4 *base = reinterpret_cast<uint4 *>(p.belief + (size_t)(block_agent0 + src) * p.agent_bytes);
-        for (uint32_t q = (uint32_t)lane; q < n16; q += 64u) base[q] = make_uint4(0u, 0u, 0u, 0u);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    zero_agent_blocks(p, __ballot(need), ~0ull, block_agent0, lane);
     if (need) {
-        g.room = (int)(drawn.x >> 24);
-        R = load_room(p, g.room);
-        g.x = drawn.x & 0xff;
-        g.y = (drawn.x >> 8) & 0xff;
-        g.z = (drawn.x >> 16) & 0xff;
-        goal = drawn.y;
-        g.facing = 0;
-        g.last_action = 0;
-        g.done = g.last_bump = g.near_wall = g.was_near_wall = false;
-        g.step_count = 0;
-        g.visited = 1;
-        g.bumps = 0;
-        g.cid = 0;
-        g.move_mask = 0;
+        reset_agent(p, drawn, g, goal, R);
         w.wx = 1ull << g.x;                                                     // :86
         w.wy = 1ull << g.y;
         w.wz = 1u << g.z;
@@ -629,16 +295,31 @@ __device__ __forceinline__ void sb_reset_wave(const Params &p, const SPlanes &pl
 #endif
 #if VN_SIMPLE_PROF
 __device__ unsigned long long g_simple_prof[16];
+#define SB_T_BEGIN                                  \
+    uint64_t prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};    \
+    uint64_t tprev = __builtin_amdgcn_s_memtime()
 #define SB_T(k)                                                    \
     do {                                                           \
         const uint64_t t_ = __builtin_amdgcn_s_memtime();          \
         prof[k] += t_ - tprev;                                     \
         tprev = t_;                                                \
     } while (0)
+#define SB_T_END \
+    if (lane == 0) simple_prof_flush(prof)
+// a stepping wave's section totals (0-6), their sum (7) and the wave count (8)
+__device__ __forceinline__ void simple_prof_flush(const uint64_t *prof) {
+    uint64_t tot = 0;
+    for (int q = 0; q < 7; ++q) {
+        atomicAdd(&g_simple_prof[q], (unsigned long long)prof[q]);
+        tot += prof[q];
+    }
+    atomicAdd(&g_simple_prof[7], tot);
+    atomicAdd(&g_simple_prof[8], 1ull);
+}
 #else
-#define SB_T(k) \
-    do {        \
-    } while (0)
+#define SB_T_BEGIN (void)0
+#define SB_T(k) (void)0
+#define SB_T_END (void)0
 #endif
 
 // vn_reset for the bit-plane layouts (line and word): 64 agents per block,
@@ -655,9 +336,10 @@ __global__ __launch_bounds__(64) void simple_bits_reset_kernel(Params p) {
     const int OD = p.obs_dim;
     float *row = sstage + lane * OD;
     const SPlanes pl = splanes(p, live ? ai : a0);
-    Agent g = unpack(live ? p.hot[ai] : make_uint4(0u, 0u, 0u, 0u));
-    uint32_t goal = live ? p.goal[ai] : 0u;
-    Room R = load_room(p, g.room);
+    Agent g;
+    uint32_t goal, next_seed;   // (next_seed: not used by a reset)
+    Room R;
+    load_agent(p, ai, live, g, goal, next_seed, R);
     SRows w;
     w.wx = w.wy = 0;
     w.wz = 0;
@@ -696,18 +378,39 @@ __global__ __launch_bounds__(64) void simple_bits_reset_kernel(Params p) {
 // wave's HBM stores stay in flight across it (a __syncthreads() would wait
 // vmcnt(0), i.e. for every store of the step to complete, before the
 // stepping wave may go on).
-#ifndef VN_LDS_BARRIER
-#define VN_LDS_BARRIER 1
-#endif
 __device__ __forceinline__ void lds_handoff() {
-#if VN_LDS_BARRIER
     asm volatile("" ::: "memory");
     __builtin_amdgcn_s_waitcnt(0xC07F);          // lgkmcnt(0) alone
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
-#else
-    __syncthreads();
-#endif
+}
+
+// The store wave of the 2-wave kernels: per step, the block's staged obs rows
+// (one contiguous span), rewards and flags from LDS buffer k & 1 to HBM.
+__device__ __forceinline__ void store_wave(const Params &p, const float *stage, const float *srew, const uint32_t *sflg,
+                                           int lane, int a0, int rows) {
+    const int OD = p.obs_dim;
+    for (int k = 0; k < p.K; ++k) {
+        lds_handoff();                     // step k staged in buffer k & 1
+        const int b = k & 1;
+        const float *st = stage + b * 64 * OD;
+        float *dst = p.obs + ((size_t)k * p.N + a0) * OD;
+        if (VN_ABLATE & 16u) {
+        } else if (!((rows * OD) & 3) && !(reinterpret_cast<uintptr_t>(dst) & 15u)) {
+            const float4 *s4 = reinterpret_cast<const float4 *>(st);
+            float4 *d4 = reinterpret_cast<float4 *>(dst);
+            for (int q = lane; q < (rows * OD) >> 2; q += 64) obs_store(d4 + q, s4[q]);
+        } else {
+            for (int q = lane; q < rows * OD; q += 64) __builtin_nontemporal_store(st[q], dst + q);
+        }
+        if (lane < rows) {
+            const size_t o = (size_t)k * p.N + a0 + lane;
+            const uint32_t f = sflg[b * 64 + lane];
+            if (p.reward) p.reward[o] = srew[b * 64 + lane];
+            if (p.term) p.term[o] = (uint8_t)(f & 1u);
+            if (p.trunc) p.trunc[o] = (uint8_t)(f >> 1);
+        }
+    }
 }
 
 
@@ -725,66 +428,14 @@ __device__ __forceinline__ void lds_handoff() {
 // stepping wave issues no output stores (the store wave does), so waiting for
 // its loads never waits for obs stores.
 // ----------------------------------------------------------------------------
-// reset of the lanes with `need` for simple_pipe_kernel: as sb_reset_wave,
-// but the MT19937 draw (a ~1.2k-step serial chain, ~15 us) is shared.  A
-// lane's draw for its next episode seed is kept in nd = {start | room << 24,
-// goal, seed, valid}.  A resetting lane whose nd is for its seed uses it; when
-// any resetting lane has none, the wave runs the chain once for EVERY live
-// lane (same instructions, so the same time as for one lane): the resetting
-// lanes take their draw and the others keep theirs for their next reset.
-// Measured: the chain was half of the kernel's time (resets ablated: 2x).
-__device__ __forceinline__ uint2 sp_reset_draw(const Params &p, bool need, bool live, uint32_t seed, int lane, uint4 &nd,
-                                               uint32_t *mt_lds) {
-    const bool have = need && nd.w == 1u && nd.z == seed;
-    uint2 drawn = have ? make_uint2(nd.x, nd.y) : make_uint2(0u, 0u);
-    if (need) nd.w = 0u;                                   // consumed: the next episode has another seed
-    if (__ballot(need && !have)) {
-        // one chain pass for the wave: a resetting lane without a draw computes
-        // this episode's; one with a draw the episode after it (seed + stride);
-        // the others their next episode's if they have none
-        const uint32_t s2 = (need && have) ? seed + p.seed_stride : seed;
-        mt_outputs_wide(s2, mt_lds + lane * MT_WS);
-        MtLdsStream mt;
-        mt.row = mt_lds + lane * MT_WS;
-        mt.seed = s2;
-        mt.used = 0;
-        mt.err = p.envc->err;
-        const uint2 d2 = live ? simple_draw_from(p.envc, mt) : make_uint2(0u, 0u);
-        if (need && !have) drawn = d2;
-        else if (live) nd = make_uint4(d2.x, d2.y, s2, 1u);
-    }
-    return drawn;
-}
-
 template <int LMAX>
 __device__ __forceinline__ void sp_reset_wave(const Params &p, const SPlanes &pl, bool need, bool live, uint32_t seed,
                                               Agent &g, uint32_t &goal, Room &R, SRows &w, float *row, int lane,
                                               int block_agent0, uint4 &nd, uint32_t *mt_lds) {
     const uint2 drawn = sp_reset_draw(p, need, live, seed, lane, nd, mt_lds);
-    uint64_t m = __ballot(need);
-    const uint32_t n16 = p.agent_bytes >> 4;
-    while (m) {
-        const int src = __ffsll((unsigned long long)m) - 1;
-        m &= m - 1;
-        uint4 *base = reinterpret_cast<uint4 *>(p.belief + (size_t)(block_agent0 + src) * p.agent_bytes);
-        for (uint32_t q = (uint32_t)lane; q < n16; q += 64u) base[q] = make_uint4(0u, 0u, 0u, 0u);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    zero_agent_blocks(p, __ballot(need), ~0ull, block_agent0, lane);
     if (need) {
-        g.room = (int)(drawn.x >> 24);
-        R = load_room(p, g.room);
-        g.x = drawn.x & 0xff;
-        g.y = (drawn.x >> 8) & 0xff;
-        g.z = (drawn.x >> 16) & 0xff;
-        goal = drawn.y;
-        g.facing = 0;
-        g.last_action = 0;
-        g.done = g.last_bump = g.near_wall = g.was_near_wall = false;
-        g.step_count = 0;
-        g.visited = 1;
-        g.bumps = 0;
-        g.cid = 0;
-        g.move_mask = 0;
+        reset_agent(p, drawn, g, goal, R);
         w.wx = 1ull << g.x;                                                     // :86
         w.wy = 1ull << g.y;
         w.wz = 1u << g.z;
@@ -804,7 +455,7 @@ struct SPend {
 template <int LMAX, bool EXT>
 __global__ __launch_bounds__(128) void simple_pipe_kernel(Params p) {
     extern __shared__ float sm[];
-    const int OD = p.obs_dim, L = p.L;
+    const int OD = p.obs_dim;
     float *stage = sm;
     float *srew = sm + 2 * 64 * OD;
     uint32_t *sflg = reinterpret_cast<uint32_t *>(srew + 2 * 64);
@@ -812,28 +463,8 @@ __global__ __launch_bounds__(128) void simple_pipe_kernel(Params p) {
     const int a0 = blockIdx.x * 64;
     const int rows = min(64, p.N - a0);
 
-    if (threadIdx.x >= 64) {                     // ---- store wave (as simple_split_kernel) ----
-        for (int k = 0; k < p.K; ++k) {
-            lds_handoff();                     // step k staged in buffer k & 1
-            const int b = k & 1;
-            const float *st = stage + b * 64 * OD;
-            float *dst = p.obs + ((size_t)k * p.N + a0) * OD;
-            if (VN_ABLATE & 16u) {
-            } else if (!((rows * OD) & 3) && !(reinterpret_cast<uintptr_t>(dst) & 15u)) {
-                const float4 *s4 = reinterpret_cast<const float4 *>(st);
-                float4 *d4 = reinterpret_cast<float4 *>(dst);
-                for (int q = lane; q < (rows * OD) >> 2; q += 64) obs_store(d4 + q, s4[q]);
-            } else {
-                for (int q = lane; q < rows * OD; q += 64) __builtin_nontemporal_store(st[q], dst + q);
-            }
-            if (lane < rows) {
-                const size_t o = (size_t)k * p.N + a0 + lane;
-                const uint32_t f = sflg[b * 64 + lane];
-                if (p.reward) p.reward[o] = srew[b * 64 + lane];
-                if (p.term) p.term[o] = (uint8_t)(f & 1u);
-                if (p.trunc) p.trunc[o] = (uint8_t)(f >> 1);
-            }
-        }
+    if (threadIdx.x >= 64) {
+        store_wave(p, stage, srew, sflg, lane, a0, rows);
         return;
     }
 
@@ -851,11 +482,11 @@ __global__ __launch_bounds__(128) void simple_pipe_kernel(Params p) {
     const int ai = a0 + lane;
     const bool live = ai < p.N;
     const SPlanes pl = splanes(p, live ? ai : a0);
-    Agent g = unpack(live ? p.hot[ai] : make_uint4(0u, 0u, 0u, 0u));
-    uint32_t goal = live ? p.goal[ai] : 0u;
-    uint32_t next_seed = live ? p.next_seed[ai] : 0u;
-    uint4 nd = live ? p.predraw[ai] : make_uint4(0u, 0u, 0u, 0u);   // draw ahead (sp_reset_wave)
-    Room R = load_room(p, g.room);
+    Agent g;
+    uint32_t goal, next_seed;
+    Room R;
+    load_agent(p, ai, live, g, goal, next_seed, R);
+    uint4 nd = live ? p.predraw[ai] : make_uint4(0u, 0u, 0u, 0u);   // draw ahead (sp_reset_draw)
     SRows w;                                     // S words + ray record at the agent's (committed) cell
     w.wx = w.wy = 0;
     w.wz = 0;
@@ -920,10 +551,7 @@ __global__ __launch_bounds__(128) void simple_pipe_kernel(Params p) {
         }
     };
     if (live && p.K > 0) premove(0);
-#if VN_SIMPLE_PROF
-    uint64_t prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t tprev = __builtin_amdgcn_s_memtime();
-#endif
+    SB_T_BEGIN;
 
     for (int k = 0; k < p.K; ++k) {
         const int b = k & 1;
@@ -1070,124 +698,14 @@ __global__ __launch_bounds__(128) void simple_pipe_kernel(Params p) {
         lds_handoff();                         // hand buffer b to the store wave
         SB_T(6);
     }
-#if VN_SIMPLE_PROF
-    if (lane == 0) {
-        uint64_t tot = 0;
-        for (int q = 0; q < 7; ++q) {
-            atomicAdd(&g_simple_prof[q], (unsigned long long)prof[q]);
-            tot += prof[q];
-        }
-        atomicAdd(&g_simple_prof[7], tot);
-        atomicAdd(&g_simple_prof[8], 1ull);
-    }
-#endif
+    SB_T_END;
     if (live) {
         if (sdirty & 1u) pl.sx[g.y * p.ph + g.z] = w.wx;
         if (sdirty & 2u) pl.sy[g.x * p.ph + g.z] = w.wy;
         if (sdirty & 4u) pl.sz[g.x * p.pd + g.y] = w.wz;
-        p.hot[ai] = pack(g);
-        p.goal[ai] = goal;
-        p.next_seed[ai] = next_seed;
+        store_agent(p, ai, g, goal, next_seed);
         p.predraw[ai] = nd;
     }
-    (void)L;
-}
-
-
-// ============================================================================
-// simpleEnv, line layout (the default for rooms up to 32 x 32 x 8, e.g. the
-// bench's 32x32x8 box).  Same belief as the bit-plane layout -- S (cells
-// stood on) and Q (edge-quirk marks), every other internal_grid value derived
-// -- but S is kept as LINES: SX[y] = 8 u32 words over z (bit x), SY[x] = 8 u32
-// words over z (bit y), 32 B each; a column's z bits (the up / down rays) are
-// bit x of the SX[y] line, so there is no third copy.  The stepping lane keeps
-// the two lines through its cell in LDS: a move along x replaces the SY line,
-// along y the SX line, along z neither; the line left is stored back if it
-// was marked.
-// Why (rocprofv3, round 3): the simpleEnv step is bound by the CUs' 64-B
-// request rate -- the address unit is busy 87-95 % of the kernel, at 5.7
-// requests per env-step, 1.1 of them the evicted S words of the word layout
-// (each move replaced 2-3 words; without those stores the kernel ran 1.4x).
-// A lane's 32-B line access is 2 x 16 B; lane pairs split it so that both
-// halves of one line go out in ONE instruction (a request per line, not per
-// half): instruction 1 moves the even lane's line, instruction 2 the odd
-// lane's, and the halves are swapped across the pair with one DPP move.
-// Every line load / store is issued every step (an out-of-range buffer offset
-// when a lane has none: no request, and the same vmcnt count on every path).
-// LDS per lane: the X and Y line (12-word stride: 16-B aligned rows).
-// QZ (edge-quirk marks) as in the bit-plane layout.
-// ============================================================================
-constexpr int SL_STRIDE = 12;   // words per LDS line slot
-constexpr uint32_t SL_OFF = 0x80000000u;   // out-of-range buffer offset: dropped
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-
-struct SLine {
-    u32x4_t h0, h1;   // words 0-3, 4-7
-};
-
-__device__ __forceinline__ uint32_t dpp_swap_pair(uint32_t v) {   // lane i <- lane i ^ 1
-    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xF, 0xF, false);
-}
-__device__ __forceinline__ u32x4_t dpp_swap_pair4(u32x4_t v) {
-    u32x4_t r;
-    r.x = dpp_swap_pair(v.x);
-    r.y = dpp_swap_pair(v.y);
-    r.z = dpp_swap_pair(v.z);
-    r.w = dpp_swap_pair(v.w);
-    return r;
-}
-
-// lane-pair line load: each lane gets the line at its byte offset `off`
-// (SL_OFF: none, zeros).  Issue and finish (the swap across the pair, which
-// needs the data) are split so the loads stay in flight across a step.  Both
-// must run with the whole wave active.
-__device__ __forceinline__ SLine sl_pair_issue(__amdgpu_buffer_rsrc_t rs, uint32_t off, bool odd) {
-    const uint32_t off_p = dpp_swap_pair(off);
-    const uint32_t ae = odd ? off_p : off, ao = odd ? off : off_p;     // the pair's even / odd line
-    const uint32_t half = odd ? 16u : 0u;
-    SLine r;   // even: h0 = own h0, h1 = partner's h0; odd: h0 = partner's h1, h1 = own h1
-    r.h0 = __builtin_amdgcn_raw_buffer_load_b128(rs, ae == SL_OFF ? SL_OFF : ae + half, 0, 0);
-    r.h1 = __builtin_amdgcn_raw_buffer_load_b128(rs, ao == SL_OFF ? SL_OFF : ao + half, 0, 0);
-    return r;
-}
-__device__ __forceinline__ SLine sl_pair_finish(const SLine &r, bool odd) {
-    const u32x4_t sw = dpp_swap_pair4(odd ? r.h0 : r.h1);
-    SLine l;
-    l.h0 = odd ? sw : r.h0;
-    l.h1 = odd ? r.h1 : sw;
-    return l;
-}
-__device__ __forceinline__ SLine sl_pair_load(__amdgpu_buffer_rsrc_t rs, uint32_t off, bool odd) {
-    return sl_pair_finish(sl_pair_issue(rs, off, odd), odd);
-}
-
-// lane-pair line store of each lane's line `l` at `off` (SL_OFF: none)
-__device__ __forceinline__ void sl_pair_store(__amdgpu_buffer_rsrc_t rs, uint32_t off, const SLine &l, bool odd) {
-    const uint32_t off_p = dpp_swap_pair(off);
-    const uint32_t ae = odd ? off_p : off, ao = odd ? off : off_p;
-    const uint32_t half = odd ? 16u : 0u;
-    const u32x4_t sw = dpp_swap_pair4(odd ? l.h0 : l.h1);   // even gets the odd lane's h0, odd the even's h1
-    __builtin_amdgcn_raw_buffer_store_b128(odd ? sw : l.h0, rs, ae == SL_OFF ? SL_OFF : ae + half, 0, 0);
-    __builtin_amdgcn_raw_buffer_store_b128(odd ? l.h1 : sw, rs, ao == SL_OFF ? SL_OFF : ao + half, 0, 0);
-}
-
-__device__ __forceinline__ void sl_lds_put(uint32_t *slot, const SLine &l) {
-    reinterpret_cast<u32x4_t *>(slot)[0] = l.h0;
-    reinterpret_cast<u32x4_t *>(slot)[1] = l.h1;
-}
-__device__ __forceinline__ SLine sl_lds_get(const uint32_t *slot) {
-    SLine l;
-    l.h0 = reinterpret_cast<const u32x4_t *>(slot)[0];
-    l.h1 = reinterpret_cast<const u32x4_t *>(slot)[1];
-    return l;
-}
-// bit z = bit b of word z (the column's S bits from the SX line)
-__device__ __forceinline__ uint32_t sl_column(const SLine &l, int b) {
-    const uint32_t w[8] = {l.h0.x, l.h0.y, l.h0.z, l.h0.w, l.h1.x, l.h1.y, l.h1.z, l.h1.w};
-    uint32_t c = 0;
-#pragma unroll
-    for (int z = 0; z < 8; ++z) c |= ((w[z] >> b) & 1u) << z;
-    return c;
 }
 
 // reset of the lanes with `need` (sp_reset_wave in the line layout): the
@@ -1199,33 +717,10 @@ __device__ __forceinline__ void sl_reset_wave(const Params &p, const SPlanes &pl
                                               int block_agent0, uint4 &nd, uint32_t *mt_lds, uint32_t *lx,
                                               uint32_t *ly) {
     const uint2 drawn = sp_reset_draw(p, need, live, seed, lane, nd, mt_lds);
-    const bool hadq = need && (g.move_mask & 1u);
-    uint64_t m = __ballot(need);
-    const uint64_t mq = __ballot(hadq);
-    while (m) {
-        const int src = __ffsll((unsigned long long)m) - 1;
-        m &= m - 1;
-        // QZ (at the end of the agent's block) is all zero unless the episode marked it
-        const uint32_t n16 = (((mq >> src) & 1ull) ? p.agent_bytes : p.qz_off) >> 4;
-        uint4 *base = reinterpret_cast<uint4 *>(p.belief + (size_t)(block_agent0 + src) * p.agent_bytes);
-        for (uint32_t q = (uint32_t)lane; q < n16; q += 64u) base[q] = make_uint4(0u, 0u, 0u, 0u);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    // QZ (at the end of the agent's block) is all zero unless the episode marked it
+    zero_agent_blocks(p, __ballot(need), __ballot(need && (g.move_mask & 1u)), block_agent0, lane);
     if (need) {
-        g.room = (int)(drawn.x >> 24);
-        R = load_room(p, g.room);
-        g.x = drawn.x & 0xff;
-        g.y = (drawn.x >> 8) & 0xff;
-        g.z = (drawn.x >> 16) & 0xff;
-        goal = drawn.y;
-        g.facing = 0;
-        g.last_action = 0;
-        g.done = g.last_bump = g.near_wall = g.was_near_wall = false;
-        g.step_count = 0;
-        g.visited = 1;
-        g.bumps = 0;
-        g.cid = 0;
-        g.move_mask = 0;
+        reset_agent(p, drawn, g, goal, R);
         w.wx = 1ull << g.x;                                                     // :86
         w.wy = 1ull << g.y;
         w.wz = 1u << g.z;
@@ -1242,7 +737,7 @@ __device__ __forceinline__ void sl_reset_wave(const Params &p, const SPlanes &pl
 template <int LMAX, bool EXT>
 __global__ __launch_bounds__(128) void simple_line_kernel(Params p) {
     extern __shared__ float sm[];
-    const int OD = p.obs_dim, L = p.L;
+    const int OD = p.obs_dim;
     float *stage = sm;
     float *srew = sm + 2 * 64 * OD;
     uint32_t *sflg = reinterpret_cast<uint32_t *>(srew + 2 * 64);
@@ -1255,28 +750,8 @@ __global__ __launch_bounds__(128) void simple_line_kernel(Params p) {
     const int a0 = blockIdx.x * 64;
     const int rows = min(64, p.N - a0);
 
-    if (threadIdx.x >= 64) {                     // ---- store wave (as simple_pipe_kernel) ----
-        for (int k = 0; k < p.K; ++k) {
-            lds_handoff();                     // step k staged in buffer k & 1
-            const int b = k & 1;
-            const float *st = stage + b * 64 * OD;
-            float *dst = p.obs + ((size_t)k * p.N + a0) * OD;
-            if (VN_ABLATE & 16u) {
-            } else if (!((rows * OD) & 3) && !(reinterpret_cast<uintptr_t>(dst) & 15u)) {
-                const float4 *s4 = reinterpret_cast<const float4 *>(st);
-                float4 *d4 = reinterpret_cast<float4 *>(dst);
-                for (int q = lane; q < (rows * OD) >> 2; q += 64) obs_store(d4 + q, s4[q]);
-            } else {
-                for (int q = lane; q < rows * OD; q += 64) __builtin_nontemporal_store(st[q], dst + q);
-            }
-            if (lane < rows) {
-                const size_t o = (size_t)k * p.N + a0 + lane;
-                const uint32_t f = sflg[b * 64 + lane];
-                if (p.reward) p.reward[o] = srew[b * 64 + lane];
-                if (p.term) p.term[o] = (uint8_t)(f & 1u);
-                if (p.trunc) p.trunc[o] = (uint8_t)(f >> 1);
-            }
-        }
+    if (threadIdx.x >= 64) {
+        store_wave(p, stage, srew, sflg, lane, a0, rows);
         return;
     }
 
@@ -1293,11 +768,11 @@ __global__ __launch_bounds__(128) void simple_line_kernel(Params p) {
     sl_build_cell_lut(clut, lane);
     if (lane < 48) srt[lane] = p.lut[TAB_SREW + lane];
     const SPlanes pl = splanes(p, live ? ai : a0);
-    Agent g = unpack(live ? p.hot[ai] : make_uint4(0u, 0u, 0u, 0u));
-    uint32_t goal = live ? p.goal[ai] : 0u;
-    uint32_t next_seed = live ? p.next_seed[ai] : 0u;
-    uint4 nd = live ? p.predraw[ai] : make_uint4(0u, 0u, 0u, 0u);   // draw ahead (sp_reset_wave)
-    Room R = load_room(p, g.room);
+    Agent g;
+    uint32_t goal, next_seed;
+    Room R;
+    load_agent(p, ai, live, g, goal, next_seed, R);
+    uint4 nd = live ? p.predraw[ai] : make_uint4(0u, 0u, 0u, 0u);   // draw ahead (sp_reset_draw)
     auto xline_off = [&](int y) { return lane_off + 32u * (uint32_t)y; };
     auto yline_off = [&](int x) { return lane_off + p.sy_off + 32u * (uint32_t)x; };
     SRows w;                                     // S words + ray record at the agent's (committed) cell
@@ -1372,10 +847,7 @@ __global__ __launch_bounds__(128) void simple_line_kernel(Params p) {
         }
     };
     if (p.K > 0) premove(0, live, false);
-#if VN_SIMPLE_PROF
-    uint64_t prof[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    uint64_t tprev = __builtin_amdgcn_s_memtime();
-#endif
+    SB_T_BEGIN;
 
     for (int k = 0; k < p.K; ++k) {
         const int b = k & 1;
@@ -1497,26 +969,13 @@ __global__ __launch_bounds__(128) void simple_line_kernel(Params p) {
         lds_handoff();                         // hand buffer b to the store wave
         SB_T(6);
     }
-#if VN_SIMPLE_PROF
-    if (lane == 0) {
-        uint64_t tot = 0;
-        for (int q = 0; q < 7; ++q) {
-            atomicAdd(&g_simple_prof[q], (unsigned long long)prof[q]);
-            tot += prof[q];
-        }
-        atomicAdd(&g_simple_prof[7], tot);
-        atomicAdd(&g_simple_prof[8], 1ull);
-    }
-#endif
+    SB_T_END;
     sl_pair_store(brs, (live && (dirty & 1u)) ? xline_off(g.y) : SL_OFF, sl_lds_get(lx), odd);
     sl_pair_store(brs, (live && (dirty & 2u)) ? yline_off(g.x) : SL_OFF, sl_lds_get(ly), odd);
     if (live) {
-        p.hot[ai] = pack(g);
-        p.goal[ai] = goal;
-        p.next_seed[ai] = next_seed;
+        store_agent(p, ai, g, goal, next_seed);
         p.predraw[ai] = nd;
     }
-    (void)L;
 }
 
 // internal_grid value of one cell from S, Q and the walls (see the layout
@@ -1570,56 +1029,69 @@ namespace vn_simple {
 
 int ensure_mt(int device) { return ensure_mt_table(device); }
 
-// The simpleEnv kernel for a call shape: the line layout's step kernel
-// (rooms <= 32 x 32 x 8), the word layout's (<= 64 x 64 x 31), the bit-plane
-// reset kernel for both, the dense-map kernel for larger rooms.
+// The simpleEnv kernel of a call shape, picked here for launch and label alike:
+// the line layout's step kernel (rooms <= 32 x 32 x 8), the word layout's
+// (<= 64 x 64 x 31), the bit-plane reset kernel for both, the dense-map kernel
+// for larger rooms; LMAX is L's bucket.
+enum Family { LINE, PIPE, BITS_RESET, DENSE };
+struct Pick {
+    Family fam;
+    int lmax;
+};
+static Pick pick(bool reset_only, int sline, int sbits, int L) {
+    const Family fam = (!reset_only && sline) ? LINE : (!reset_only && sbits) ? PIPE : sbits ? BITS_RESET : DENSE;
+    return {fam, L <= 4 ? 4 : L <= 8 ? 8 : L <= 10 ? 10 : 16};
+}
+// LDS: one wave's obs rows; the 2-wave step kernels double-buffer them with the
+// rewards and flags and keep the MT rows (PIPE), and the lines, the cell
+// table and the reward table as well (LINE)
+static size_t lds_bytes(Family fam, int obs_dim) {
+    const size_t rows = (size_t)64 * obs_dim * sizeof(float);
+    const size_t pipe = 2 * rows + 2 * 64 * 8 + 64 * MT_WS * 4;
+    return fam == LINE ? pipe + (4 + 3 * 64 * SL_STRIDE) * 4 + SL_CLUT * 16 + 48 * 4 : fam == PIPE ? pipe : rows;
+}
+
 template <int LM>
-static int launch_lm(bool reset_only, int sline, int sbits, int N, int obs_dim, const Params &p, hipStream_t s) {
-    if (!reset_only && sline) {
-        // stepping wave + store wave per 64 agents (simple_line_kernel)
-        const size_t lds = (size_t)2 * 64 * obs_dim * sizeof(float) + 2 * 64 * 8 + 64 * MT_WS * 4 +
-                           (4 + 3 * 64 * SL_STRIDE) * 4 + SL_CLUT * 16 + 48 * 4;
-        const dim3 grid((unsigned)((N + 63) / 64));
+static void launch_lm(Family fam, bool reset_only, dim3 grid, size_t lds, const Params &p, hipStream_t s) {
+    switch (fam) {
+    case LINE:   // stepping wave + store wave per 64 agents
         if (p.actions) hipLaunchKernelGGL((simple_line_kernel<LM, true>), grid, dim3(128), lds, s, p);
         else hipLaunchKernelGGL((simple_line_kernel<LM, false>), grid, dim3(128), lds, s, p);
-    } else if (!reset_only && sbits) {
-        // software-pipelined stepping wave + store wave per 64 agents (simple_pipe_kernel)
-        const size_t lds = (size_t)2 * 64 * obs_dim * sizeof(float) + 2 * 64 * 8 + 64 * MT_WS * 4;
-        const dim3 grid((unsigned)((N + 63) / 64));
+        break;
+    case PIPE:   // software-pipelined stepping wave + store wave per 64 agents
         if (p.actions) hipLaunchKernelGGL((simple_pipe_kernel<LM, true>), grid, dim3(128), lds, s, p);
         else hipLaunchKernelGGL((simple_pipe_kernel<LM, false>), grid, dim3(128), lds, s, p);
-    } else if (sbits) {
-        const size_t lds = (size_t)64 * obs_dim * sizeof(float);
-        hipLaunchKernelGGL((simple_bits_reset_kernel<LM>), dim3((unsigned)((N + 63) / 64)), dim3(64), lds, s, p);
-    } else {
-        const size_t lds = (size_t)64 * obs_dim * sizeof(float);
-        const dim3 grid((unsigned)((N + 63) / 64));
+        break;
+    case BITS_RESET:
+        hipLaunchKernelGGL((simple_bits_reset_kernel<LM>), grid, dim3(64), lds, s, p);
+        break;
+    case DENSE:
         if (reset_only) hipLaunchKernelGGL((simple_kernel<true>), grid, dim3(64), lds, s, p);
         else hipLaunchKernelGGL((simple_kernel<false>), grid, dim3(64), lds, s, p);
+        break;
     }
-    VN_HIP(hipGetLastError());
-    return VN_OK;
 }
 
 int launch(bool reset_only, int sline, int sbits, int L, int N, int obs_dim, const void *params, hipStream_t s) {
     const Params &p = *static_cast<const Params *>(params);
-    if (L <= 4) return launch_lm<4>(reset_only, sline, sbits, N, obs_dim, p, s);
-    if (L <= 8) return launch_lm<8>(reset_only, sline, sbits, N, obs_dim, p, s);
-    if (L <= 10) return launch_lm<10>(reset_only, sline, sbits, N, obs_dim, p, s);
-    return launch_lm<16>(reset_only, sline, sbits, N, obs_dim, p, s);
+    const Pick k = pick(reset_only, sline, sbits, L);
+    const dim3 grid((unsigned)((N + 63) / 64));
+    const size_t lds = lds_bytes(k.fam, obs_dim);
+    if (k.lmax == 4) launch_lm<4>(k.fam, reset_only, grid, lds, p, s);
+    else if (k.lmax == 8) launch_lm<8>(k.fam, reset_only, grid, lds, p, s);
+    else if (k.lmax == 10) launch_lm<10>(k.fam, reset_only, grid, lds, p, s);
+    else launch_lm<16>(k.fam, reset_only, grid, lds, p, s);
+    VN_HIP(hipGetLastError());
+    return VN_OK;
 }
 
 std::string label(bool reset_only, bool ext, int sline, int sbits, int L) {
     char buf[96];
-    const int lmax = L <= 4 ? 4 : L <= 8 ? 8 : L <= 10 ? 10 : 16;
-    if (!reset_only && sline)
-        std::snprintf(buf, sizeof(buf), "simple_line_kernel<%d, %s>", lmax, ext ? "true" : "false");
-    else if (!reset_only && sbits)
-        std::snprintf(buf, sizeof(buf), "simple_pipe_kernel<%d, %s>", lmax, ext ? "true" : "false");
-    else if (sbits)
-        std::snprintf(buf, sizeof(buf), "simple_bits_reset_kernel<%d>", lmax);
-    else
-        std::snprintf(buf, sizeof(buf), "simple_kernel<%s>", reset_only ? "true" : "false");
+    const Pick k = pick(reset_only, sline, sbits, L);
+    const char *tf = (k.fam == DENSE ? reset_only : ext) ? "true" : "false";
+    if (k.fam == DENSE) std::snprintf(buf, sizeof(buf), "simple_kernel<%s>", tf);
+    else if (k.fam == BITS_RESET) std::snprintf(buf, sizeof(buf), "simple_bits_reset_kernel<%d>", k.lmax);
+    else std::snprintf(buf, sizeof(buf), "simple_%s_kernel<%d, %s>", k.fam == LINE ? "line" : "pipe", k.lmax, tf);
     return buf;
 }
 

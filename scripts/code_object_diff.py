@@ -8,12 +8,19 @@ objects (``c_mt_g`` and the like) and a hash of ``.text``.  Units are matched
 by their kernel sets.  Exit status 0 when both libraries hold the same kernel
 symbols and every unit with kernels has a byte-identical ``.text``.
 
+A unit whose hash differs gets a per-function report (``functions``): every
+function symbol of ``.text`` is "identical" when its size and its disassembly
+agree with addresses dropped and the literal of the PC-relative add after
+``s_getpc_b64`` masked (that literal, the distance to the unit's constant
+tables or to a callee, shifts with any size change elsewhere in the unit).
+
   python scripts/code_object_diff.py old/libvoxnav.so new/libvoxnav.so
 """
 from __future__ import annotations
 
 import hashlib
 import json
+import re
 import subprocess
 import sys
 import tempfile
@@ -45,8 +52,44 @@ def units(so: Path):
             objects = sorted(s for s in syms if not s.endswith(".kd") and s not in kernels
                              and not s.startswith("__hip_cuid_"))
             out.append({"kernels": kernels, "objects": objects, "text_bytes": len(blob),
-                        "text_sha256": hashlib.sha256(blob).hexdigest()})
+                        "text_sha256": hashlib.sha256(blob).hexdigest(), "elf": co})
     return out
+
+
+def functions(elf: bytes):
+    """{function symbol of .text: (size, instructions without addresses and PC-relative literals)}"""
+    with tempfile.TemporaryDirectory() as td:
+        f = Path(td) / "co.elf"
+        f.write_bytes(elf)
+        objdump = [str(LLVM / "llvm-objdump"), "--no-show-raw-insn", "--no-leading-addr"]
+        tab = subprocess.run([*objdump, "-t", str(f)], capture_output=True, text=True, check=True).stdout
+        dis = subprocess.run([*objdump, "-d", str(f)], capture_output=True, text=True, check=True).stdout
+    size = {ln.split()[-1]: int(ln.split(".text")[1].split()[0], 16) for ln in tab.splitlines() if " F .text" in ln}
+    out, cur, pc = {}, None, 0
+    for ln in dis.splitlines():
+        head = re.match(r"^[0-9a-f]* ?<(.+)>:$", ln)
+        if head:
+            cur = out.setdefault(head.group(1), []) if head.group(1) in size else None
+            continue
+        ins = ln.split("//")[0].strip()
+        if cur is None or not ins:
+            continue
+        # s_getpc_b64, then s_add_u32 / s_addc_u32 with the literal
+        pc = 2 if ins.startswith("s_getpc_b64") else pc - 1
+        if pc in (0, 1) and ins.startswith(("s_add_u32", "s_addc_u32")):
+            ins = ins.rsplit(",", 1)[0] + ", <pcrel>"
+        cur.append(ins)
+    return {k: (size[k], v) for k, v in out.items()}
+
+
+def function_report(old: bytes, new: bytes):
+    a, b = functions(old), functions(new)
+    rep = {"identical": sorted(k for k in a if a[k] == b.get(k)), "changed": {}, "only_old": sorted(set(a) - set(b)),
+           "only_new": sorted(set(b) - set(a))}
+    for k in sorted(set(a) & set(b)):
+        if a[k] != b[k]:
+            rep["changed"][k] = {"bytes": [a[k][0], b[k][0]], "instructions": [len(a[k][1]), len(b[k][1])]}
+    return rep
 
 
 def main(old: Path, new: Path) -> int:
@@ -61,6 +104,8 @@ def main(old: Path, new: Path) -> int:
         same = v is not None and v["text_sha256"] == u["text_sha256"] and v["objects"] == u["objects"]
         ok = ok and (same or not u["kernels"])
         rep["units"].append({"kernels": len(u["kernels"]), "text_bytes": u["text_bytes"], "identical": same})
+        if v is not None and v["text_sha256"] != u["text_sha256"]:
+            rep["units"][-1].update(text_bytes_new=v["text_bytes"], functions=function_report(u["elf"], v["elf"]))
     rep["kernel_free_units_new"] = [{"text_bytes": u["text_bytes"], "objects": u["objects"]}
                                     for u in b if not u["kernels"]]
     rep["ok"] = ok

@@ -92,7 +92,9 @@ def test_simple_random_rollout_matches_oracle(voxnav, src, L, N, K):
 
 # the word-layout pipelined kernel (simple_pipe_kernel: the default for rooms
 # higher than 8 or wider / deeper than 32) on rooms the line layout takes by default
-PIPE_CASES = [("box:8x8x4", 4, 300, 200), ("set:P2_training", 4, 1024, 250), ("ctor:12x10x6", 10, 256, 200)]
+# (L = 7 and 16: the LMAX buckets 8 -- with L != LMAX -- and 16, as in SIMPLE_CASES)
+PIPE_CASES = [("box:8x8x4", 4, 300, 200), ("set:P2_training", 4, 1024, 250), ("ctor:12x10x6", 10, 256, 200),
+              ("set:P1_training", 7, 200, 150), ("file:P3_training/kitchen2.txt", 16, 256, 200)]
 WORD_LAYOUT = {"simple_layout": 1}
 DENSE_LAYOUT = {"simple_layout": 2}
 
