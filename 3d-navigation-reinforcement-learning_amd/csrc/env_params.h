@@ -2,7 +2,8 @@
 // hands the two kernel units: the launch parameters (Params), the
 // env-constant block the reset path reads from device memory (EnvConst), and
 // the units' host interfaces (vn_cubic: voxnav_env.hip, vn_simple:
-// voxnav_simple.hip, vn_state: voxnav_state.hip, vn_episode: voxnav_episode.hip).  No device code and no
+// voxnav_simple.hip, vn_state: voxnav_state.hip, vn_episode: voxnav_episode.hip,
+// vn_gather: voxnav_gather.hip, vn_plan: voxnav_plan.hip).  No device code and no
 // device symbol.  The structs are
 // in an anonymous namespace: each unit has its own (identical) copy, so
 // Params crosses the unit boundary as a pointer.
@@ -116,6 +117,13 @@ namespace vn_gather {
 int copy_agents(const void *dst, const void *src, const void *parts, const int32_t *src_index, const int64_t *seeds,
                 int32_t *n_rejected, hipStream_t s);
 }  // namespace vn_gather
+
+// The frontier planner (voxnav_plan.hip; vn_plan_frontier; the rule is
+// env_route.h): CubicEnv envs whose padded width and depth are at most 64 (the
+// caller has checked).  One launch; reads the env, writes actions / dist only.
+namespace vn_plan {
+int frontier(const void *params, const uint8_t *mask, int32_t *actions, int32_t *dist, int pw, int pd, hipStream_t s);
+}  // namespace vn_plan
 
 // The simpleEnv unit (voxnav_simple.hip).
 namespace vn_simple {

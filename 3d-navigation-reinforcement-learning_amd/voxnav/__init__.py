@@ -17,6 +17,7 @@ include/voxnav.h.  Public API:
   save_checkpoint / load_checkpoint   SB3 .zip layout, Grid_Train naming
   checkpoint.save_env_state / load_env_state   an env's agents (.npz: portable exports or a raw snapshot)
   branch.fan_out / branch.evaluate_plans   copies of chosen agents in a wider env; the returns of K-step action plans
+  planner.FrontierExplorer / planner.evaluate_planner   the frontier-exploration baseline from the agents' belief maps
   sharding            multi-GPU agent sharding helpers
 """
 from . import rooms  # noqa: F401

@@ -361,6 +361,33 @@ class BatchedGridEnv:
         self._was_reset = True
         return rej
 
+    def plan_frontier(self, mask: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                      return_dist: bool = False):
+        """The frontier planner (CubicEnv variant, padded rooms of at most
+        64 x 64; ``vn_plan_frontier``): per agent the first action of a
+        shortest path through cells it knows to be free to the nearest cell
+        that is known free and not yet visited, from its own belief map on the
+        device.  Returns actions int32 [N] (``out`` if given; rows of agents
+        without ``mask[i]`` are left as they were, zero in a fresh tensor);
+        with ``return_dist`` also dist int32 [N]: the number of steps to that
+        cell, or -1 where none is reachable and the action is the fallback
+        (the least-visited passable neighbour, 0 if there is none).  Reads the
+        env only; stream-ordered, no host sync."""
+        if not self._was_reset:
+            raise RuntimeError("call reset() before plan_frontier()")
+        N = self.num_agents
+        if out is None:
+            out = torch.zeros(N, dtype=torch.int32, device=self.device)
+        elif out.dtype != torch.int32 or tuple(out.shape) != (N,) or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"out: expected contiguous int32 {(N,)} on {self.device}")
+        m = None
+        if mask is not None:
+            m = torch.as_tensor(mask).to(device=self.device, dtype=torch.uint8).reshape(N).contiguous()
+        dist = torch.full((N,), -1, dtype=torch.int32, device=self.device) if return_dist else None
+        _native.check(self.lib.vn_plan_frontier(self._h, _ptr(m), _ptr(out), _ptr(dist), self._stream()),
+                      "vn_plan_frontier")
+        return (out, dist) if return_dist else out
+
     def _check_rollout(self, out: Rollout, K: int, reward_f64: bool):
         """A caller-owned [K, N, ...] rollout chunk: the kernel writes all K
         steps, so a short or mistyped buffer is refused here."""

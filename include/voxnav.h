@@ -345,6 +345,43 @@ int vn_copy_agents(VnEnv *dst, const VnEnv *src, const int32_t *src_index, const
                    int32_t *n_rejected, void *stream);
 
 /*
+ * The frontier planner (CubicEnv variant): for every agent the first action
+ * of a shortest path, through cells it knows to be free, to the nearest cell
+ * that is known free and not yet visited.  No reference counterpart (the
+ * reference has no scripted policy); the classical frontier-exploration
+ * baseline, computed on the device from the agent's own belief map.
+ *
+ * The rule.  Agent i has room (W, D, H), cell a and facing f; v(c) is what
+ * vn_export_belief returns for a cell c of its room: -2 wall, -1 unknown,
+ * 0 known free and unvisited, n >= 1 visited.
+ *   passable(c)  c is inside the room and v(c) >= 0 (unknown cells are not
+ *                passable: the planner uses only what the agent knows)
+ *   target(c)    v(c) = 0
+ *   flood        R_0 = the targets; R_j = (R_j-1 and the six-neighbours of
+ *                its cells) that are passable
+ *   n_k          k = 0..5: the cell action k moves to from a under facing f
+ *                (do_action, envs/CubicEnv.py:135-153: 0-3 forward / right /
+ *                backward / left relative to f, 4 is +z, 5 is -z)
+ * Found: with j the smallest index such that some passable n_k is in R_j,
+ * actions[i] is the lowest such k and dist[i] = j + 1, the number of steps to
+ * the target.  Fallback, when the flood stops growing before it reaches a
+ * passable n_k: actions[i] is the k whose passable n_k has the smallest
+ * v(n_k), ties to the lowest k, or 0 if no n_k is passable; dist[i] = -1.
+ * The planner never proposes a move into a cell it does not know to be free,
+ * so it never bumps except through that last action-0 case.
+ *
+ *   mask     device u8 [N] or NULL = all; rows of unmasked agents are left
+ *            untouched
+ *   actions  device i32 [N]
+ *   dist     device i32 [N], may be NULL
+ * One launch, stream-ordered, no host synchronisation; nothing of the env is
+ * written.  VN_ERR_INVALID, with nothing launched and the reason in
+ * vn_last_error(): NULL env or actions; a simpleEnv env; an env whose padded
+ * width or depth (VnInfo pad_w, pad_d) exceeds 64.
+ */
+int vn_plan_frontier(VnEnv *env, const uint8_t *mask, int32_t *actions, int32_t *dist, void *stream);
+
+/*
  * Episode records (both variants): what the reference reports at every
  * episode end -- "Goal Reached! Explored X % after N Steps" / "Truncated
  * after N Steps, with B Bumps and X % of cells discovered"
