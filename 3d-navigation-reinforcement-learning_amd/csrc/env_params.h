@@ -59,7 +59,8 @@ struct Params {
     const int64_t *seeds;    // reset-only launches
     const uint8_t *mask;
     uint32_t ablate;         // unused (ablations are the compile-time VN_ABLATE)
-    int prio;                // step kernel: issue priority (bits, VnTuning::prio; default 67)
+    int prio;                // step kernel: issue priority (bits, VnTuning::prio; default 67); vn_cubic::launch adds
+                             // its own bits above them (window record, base level, bits 12..31 the launch's tag)
     int dflush;              // step kernel: a step's obs flush after the next step's load issue (VnTuning::dflush)
     // simpleEnv variant
     int variant, obs_dim, pd;

@@ -138,7 +138,18 @@ __device__ __forceinline__ int sense_observe(const Params &p, int8_t *map, uint6
     // ---- plane rows: span, cached words, new marks ----
     uint64_t pn[2] = {0, 0};
     int pofs = 0;
-    if (q < 2) {
+    RT pmr = 0;                             // PC: the span mask, in the row's own width
+    if constexpr (PC) {
+        // a plane row is one RT word (rooms of at most 8 * sizeof(RT) columns): the marked span
+        // [pa, pb] lies inside it, so mask and merge are one word of that width
+        if (q < 2) {
+            const bool xr = q == 0;
+            const int nfp1 = xr ? ry.nf[0] : ry.nf[2], nfm1 = xr ? ry.nf[1] : ry.nf[3];
+            const bool whp = xr ? ry.wh[0] : ry.wh[2], whm = xr ? ry.wh[1] : ry.wh[3];
+            const int a = pcoord - nfm1 - (whm ? 1 : 0), b = pcoord + nfp1 + (whp ? 1 : 0);
+            pmr = (RT)((RT)~(RT)0 >> (8 * (int)sizeof(RT) - 1 - (b - a))) << a;
+        }
+    } else if (q < 2) {
         const bool xr = q == 0;
         const int nw = xr ? p.nwx : p.nwy;
         nfp = xr ? ry.nf[0] : ry.nf[2];
@@ -155,11 +166,7 @@ __device__ __forceinline__ int sense_observe(const Params &p, int8_t *map, uint6
             const int lo = pa - base < 0 ? 0 : pa - base, hi = pb - base > 63 ? 63 : pb - base;
             pm[w] = (w == 0 || pw0 + 1 <= pwend) && hi >= lo ? ((~0ull) >> (63 - (hi - lo))) << lo : 0ull;
         }
-        if (PC) {                          // nw == 1: the row word is in LDS
-            pc_.w[0] = prw;
-            pc_.w[1] = 0ull;
-            pc_.w0 = 0;
-        } else if (FRESH) {                // planes were cleared by the reset
+        if (FRESH) {                // planes were cleared by the reset
             pc_.row = rowi;
             pc_.w0 = nw <= 2 ? 0 : pw0;
             pc_.w[0] = pc_.w[1] = 0ull;
@@ -242,9 +249,9 @@ __device__ __forceinline__ int sense_observe(const Params &p, int8_t *map, uint6
     if constexpr (PC) {
         uint32_t pd = 0;
         if (q < 2) {
-            const uint64_t nv = pn[0] | pm[0];
-            if (nv != pn[0]) {
-                *prow_lds = (RT)nv;
+            const RT nv = prw | pmr;
+            if (nv != prw) {
+                *prow_lds = nv;
                 pd = 1u << (q == 0 ? (y & 3) : 4 + (x & 3));
             }
         }

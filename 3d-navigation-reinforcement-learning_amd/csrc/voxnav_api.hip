@@ -99,7 +99,7 @@ struct DeviceGuard {
 // changes it on a live env: scripts/ab_same.py); the caller sets its pointers.
 Params call_params(const VnEnv *e) {
     Params p = e->params;
-    p.prio = e->tuning.prio;       // bit 0: the step's load issue, 1: the obs flush, 6: rotating base
+    p.prio = e->tuning.prio;       // bit 0: the step's load issue, 1: the obs flush, 6: base level (2: the rotation)
     p.dflush = e->tuning.dflush;   // bit 0: the deferred obs flush in the byte-mark kernels (PCM 3), bit 1: in the plane-set ones
     p.wrec_k = e->tuning.wrec_k;   // launches of at most this many steps write the window record
     return p;
@@ -115,7 +115,7 @@ int launch_env(bool reset_only, VnEnv *e, const Params &p, hipStream_t s) {
 // the defaults of every VnTuning field, here only (vn_tuning_default)
 constexpr VnTuning kTuningDefault = {/*pcache_cap*/ -1, /*defer*/ -1, /*simple_layout*/ 0, /*prio*/ 67,
                                      /*dflush*/ VN_DFLUSH_DEFAULT, /*wrec_k*/ VN_WREC_K_DEFAULT, /*wrec_early*/ 1};
-constexpr int PRIO_USER_BITS = 1 | 2 | 64;   // what env_kernel decodes of VnTuning::prio (vn_cubic::launch adds PRIO_WREC_*)
+constexpr int PRIO_USER_BITS = 1 | 2 | 4 | 64;   // what env_kernel decodes of VnTuning::prio (vn_cubic::launch adds its own bits)
 
 int check_tuning(const VnTuning &t) {
     if (t.pcache_cap < -1 || t.pcache_cap > 2)

@@ -136,10 +136,60 @@ constexpr uint32_t kMoveDir = (2u << 0) | (0u << 2) | (3u << 4) | (1u << 6)     
 // box rooms +3.3 % at 20- and 128-step launches, +0.7 % one-step; P-set rooms
 // +0-1 %.  Also priority on the reward stores, the shift commit, the launch's
 // flush, or level 1 / 2 on the issue: no better.  Runtime switch per call:
-// VnTuning::prio bit 0 (issue) / bit 1 (flush) / bit 6 (the rotating base
-// level in env_kernel), default 67.
+// VnTuning::prio bit 0 (issue) / bit 1 (flush) / bit 6 (a base level 0..2
+// between the two, plane-set kernels, launches of >= 8 steps: the number of
+// the SIMD's other waves that are ahead of this one, wave_progress below; with
+// bit 2 the open-loop rotation over the CU's blocks that it replaced), default 67.
+// One runtime level dispatch per step (vn_setprio: the instruction takes an
+// immediate): after the issue section; the flush's level stays until the
+// next step's issue section raises it (a few instructions later).
 constexpr int kPrioIssue = 3;   // while the step's move is computed and its loads issued
 constexpr int kPrioFlush = 2;   // while the obs flush's stores are issued
+// Params::prio bits the host sets (vn_cubic::launch), beside env_window.h's PRIO_WREC_*:
+constexpr int PRIO_ROTATE = 4;          // (user bit) the base level is the open-loop rotation
+constexpr int PRIO_BASE = 512;          // a base level applies: bit 6, a plane-set kernel, K >= 8
+constexpr int PRIO_TAG_SHIFT = 12;      // bits 12..31: the launch's tag in the progress table
+
+// The progress table of the closed-loop base level: one word per hardware
+// wave slot of the device, indexed by where the wave really runs (XCC_ID;
+// HW_ID's SE / SH / CU bits 8-15, SIMD bits 4-5, wave id bits 0-2: gfx950 has
+// 8 wave slots per SIMD), never by an assumed dispatch order.  A word is
+// launch tag << 8 | 4-step blocks the wave has completed (saturating at 255).
+// After each block, behind its reward stores, the wave reads its SIMD's row
+// of 8 words, takes as the next block's level the number of words of its
+// launch that have completed at least as many blocks as it now has -- the
+// mates that finished this block before it -- clamped to 2, and lane 0 stores
+// the wave's own word (an ordinary vector store, through to L2).  The row is
+// wave-uniform, so it is one scalar load: it holds no vector register (the
+// plane-set kernels have none to spare at 4 waves per SIMD; a row kept in one
+// cost 2 spilled VGPRs) and lgkmcnt does not order it behind the step's
+// vector stores.  An invalidate of the scalar cache goes ahead of it (the step
+// loop makes no other scalar load); the row then comes from the XCD's L2,
+// which every wave of the SIMD writes through to.  Words of another tag (an
+// earlier launch, another env of the device, a finished wave: it clears its
+// word) are ignored; nothing waits on, polls or loops over the table, and a
+// wrong or missing word costs a priority only.  DESIGN.md 7.19.
+constexpr int kProgRow = 8;
+__device__ __attribute__((aligned(64))) unsigned int g_wave_progress[8 * 256 * 4 * kProgRow];
+typedef uint32_t ProgRow __attribute__((ext_vector_type(8)));
+// the wave's word index: its SIMD's row is [idx & ~7, idx | 7]
+__device__ __forceinline__ uint32_t wave_progress_index() {
+    const uint32_t hw = __builtin_amdgcn_s_getreg((31 << 11) | 4);      // HW_ID
+    const uint32_t xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);    // XCC_ID
+    return ((((xcc & 7u) << 8 | ((hw >> 8) & 0xffu)) << 2 | ((hw >> 4) & 3u)) << 3) | (hw & 7u);
+}
+__device__ __forceinline__ ProgRow wave_progress_row(uint32_t idx) {
+    typedef const volatile ProgRow __attribute__((address_space(4))) *RowPtr;   // uniform: a scalar load, kept in place
+    __builtin_amdgcn_s_dcache_inv();
+    __builtin_amdgcn_s_waitcnt(0xc07f);                                         // lgkmcnt(0): the invalidate is done
+    return *(RowPtr)(g_wave_progress + (idx & ~(kProgRow - 1u)));
+}
+__device__ __forceinline__ int wave_progress_level(ProgRow r, uint32_t me) {
+    int n = 0;
+#pragma unroll
+    for (int w = 0; w < kProgRow; ++w) n += (r[w] >= me && (r[w] ^ me) < 256u) ? 1 : 0;
+    return n < 2 ? n : 2;
+}
 // s_setprio with a wave-uniform runtime level (the instruction takes an immediate)
 __device__ __forceinline__ void vn_setprio(int v) {
     if (v <= 0) __builtin_amdgcn_s_setprio(0);
@@ -193,7 +243,9 @@ __device__ __forceinline__ void wave_obs_flush(const Params &p, const uint32_t *
             }
         }
     }
-    if (p.prio & 2) vn_setprio(bprio);
+    // back to the base level: the deferred flush sits between the issue section and the
+    // sensing; the in-step flush ends the step, and the next issue section follows at once
+    if (DFL ? (p.prio & 2) : (p.prio & 3) == 2) vn_setprio(bprio);
 }
 
 #if VN_ENV_PROF || VN_ENV_WT
@@ -433,13 +485,23 @@ void env_kernel(Params p) {
     // profiles/r05/env_wave_times_rotating.log).  Paired A/B
     // (profiles/r05/ab_rotating_prio_paired.log): box +3.0 % (20-step) /
     // +1.5 % (128-step); the byte-mark kernels -0.5 %, so plane-set only.
-    // VnTuning::prio bit 6 (default on).
-    const int drank = (int)(blockIdx.x / max(1u, gridDim.x / 4u));
+    // That rotation is open-loop (VnTuning::prio bit 2 still selects it); the
+    // default takes the level from the progress of the SIMD's waves instead
+    // (wave_progress above).  The host folds "bit 6, a launch of
+    // >= 8 steps" into PRIO_BASE.
+    const bool steer = PC && (p.prio & PRIO_BASE) && !(p.prio & PRIO_ROTATE);
+    // (neither mode keeps a scalar across the step loop for this: the dispatch rank and the
+    // wave's table index are worked out where they are used, once per 4-step block)
     auto base_prio = [&](int kk) -> int {
-        return (PC && (p.prio & 64) && p.K >= 8) ? min((drank + (kk >> 2)) & 3, 2) : 0;   // launches of >= 8 steps
+        if (!(PC && (p.prio & PRIO_BASE) && (p.prio & PRIO_ROTATE))) return 0;
+        const int drank = (int)(blockIdx.x / max(1u, gridDim.x / 4u));
+        return min((drank + (kk >> 2)) & 3, 2);
     };
     int bprio = base_prio(0);
     if (bprio) vn_setprio(bprio);
+    auto progress_word = [&](int kk) -> uint32_t {   // launch tag << 8 | blocks completed before step kk
+        return (((uint32_t)p.prio >> PRIO_TAG_SHIFT) << 8) | (uint32_t)min((kk + 3) >> 2, 255);
+    };
     // DFL: chosen by the host (launch_ph: VnTuning::dflush, launches of more
     // than one step, every wave full); a separate instantiation, so the
     // waits of the loop see the same five flush stores on every path
@@ -452,10 +514,10 @@ void env_kernel(Params p) {
             const uint32_t sel = (uint32_t)(tb >> 2) & 3u;
             acts = sel == 0u ? a16[0] : sel == 1u ? a16[1] : sel == 2u ? a16[2] : a16[3];
         }
-        if (PC && (p.prio & 64) && p.K >= 8) {   // the rotating base level, every 4-step block
+        if (PC && (p.prio & PRIO_BASE) && (p.prio & PRIO_ROTATE)) {   // the rotating base level, every 4-step block
             bprio = base_prio(k);
             vn_setprio(bprio);
-        }
+        }                                    // (the closed loop's level: set at the previous block's end)
         const int jn = (4 - (int)(tb & 3u)) < (p.K - k) ? (4 - (int)(tb & 3u)) : (p.K - k);
         uint64_t ev4 = 0;                                     // STRIPE_R: reward events by slot (t & 3), 16 bits each
         const int kb = k;
@@ -516,7 +578,8 @@ void env_kernel(Params p) {
                     rec = p.rays[R.ray_off + (uint32_t)((g.x * R.D + g.y) * R.H + g.z)];
                 }
                 if (!PC) plane_prefetch<PH>(p, map, pc_, g.x, g.y, g.z, q);
-                if (p.prio & 1) vn_setprio(bprio);
+                // (the deferred flush follows at its own level and restores the base level)
+                if ((p.prio & 1) && !(DFL && (p.prio & 2))) vn_setprio(bprio);
                 // the previous step's rows, behind this step's loads (k == 0: into scratch);
                 // the compiler barrier keeps the loads above (the plane rows' conditional
                 // block included) ahead of the five stores
@@ -654,6 +717,16 @@ void env_kernel(Params p) {
             }
             ENV_T(6);
         }
+        // the next block's base level: the SIMD's waves of this launch that completed this block
+        // before this wave did (the next step's issue section applies it); then the wave's own
+        // progress word, behind the block's output stores
+        if (PC && steer && k < p.K) {   // another block follows
+            bprio = wave_progress_level(wave_progress_row(wave_progress_index()), progress_word(k));
+            if (!(p.prio & 1)) vn_setprio(bprio);
+        }
+        if (PC && steer && lane == 0)
+            __hip_atomic_store(&g_wave_progress[wave_progress_index()], k < p.K ? progress_word(k) : 0u,
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (0: a finished wave is nobody's mate)
     }
     // the launch's last step's rows
     if constexpr (DFL) wave_obs_flush<CW, true>(p, wst, tab, p.K - 1, wave_agent0, nvalid, lane, abl_sink, bprio);
@@ -873,6 +946,12 @@ int launch(bool reset_only, int defer, int wrec_early, bool *wrec_written, const
     if (p.K <= p.wrec_k) p.prio |= PRIO_WREC_SAVE;
     if (*wrec_written && wrec_early) p.prio |= PRIO_WREC_EARLY;
     *wrec_written = p.K <= p.wrec_k;
+    // the base level (VnTuning::prio bit 6): plane-set kernels, launches of >= 8 steps; the closed
+    // loop's table tells launches apart by a tag, a process-wide launch count
+    if ((p.prio & 64) && p.K >= 8 && (pcm == 1 || pcm == 2)) {
+        static std::atomic<uint32_t> launches{0};
+        p.prio |= PRIO_BASE | (int)((launches.fetch_add(1u) + 1u) << PRIO_TAG_SHIFT);
+    }
     return launch_pcm<false>(pcm, p, s);
 }
 

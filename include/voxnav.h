@@ -118,8 +118,11 @@ typedef struct VnTuning {
                                 map                                                */
     /* changeable on a live env (vn_set_tuning; they only pick a launch) */
     int32_t prio;            /* step kernel issue priority, bits: 1 the step's load
-                                issue, 2 the obs flush, 64 the rotating base level
-                                of launches of >= 8 steps; default 67              */
+                                issue, 2 the obs flush, 64 a base level among the
+                                SIMD's waves in launches of >= 8 steps (the wave
+                                behind its mates goes first), 4 that level from the
+                                open-loop rotation over a CU's blocks instead;
+                                default 67                                         */
     int32_t dflush;          /* deferred obs flush (a step's flush after the next
                                 step's load issue; launches of more than one step),
                                 bits: 1 in the byte-mark kernels, 2 in the plane-set
@@ -135,7 +138,7 @@ typedef struct VnTuning {
 int vn_tuning_default(VnTuning *out);
 /* vn_create with a tuning (NULL = defaults).  VN_ERR_INVALID for a field out
  * of range: pcache_cap in {-1, 0, 1, 2}, defer in {-1, 0}, simple_layout in
- * {0, 1, 2}, prio a subset of bits 67, dflush in 0..3, wrec_k >= 0,
+ * {0, 1, 2}, prio a subset of bits 71, dflush in 0..3, wrec_k >= 0,
  * wrec_early in {0, 1}. */
 int vn_create_tuned(const VnRoomSet *rooms, int32_t n_agents, const VnConfig *cfg, int32_t device,
                     const VnTuning *tuning, VnEnv **out);

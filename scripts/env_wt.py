@@ -79,3 +79,23 @@ for rep in range(3):
         print(f"  {len(cnt)} SIMDs, waves per SIMD {np.bincount(cnt)[1:]}; per SIMD last end p10 "
               f"{np.percentile(last, 10):.1f} p50 {np.median(last):.1f} max {last.max():.1f}; first end p50 "
               f"{np.median(first):.1f}")
+        # the tail split in two: waves grouped by the SIMD they ran on (XCC_ID; HW_ID's SE / SH / CU
+        # bits 8-15 and SIMD bits 4-5).  (group max - group mean) is unfairness among a SIMD's
+        # waves, which a priority can remove; a late group mean is a whole SIMD / CU running late,
+        # which it cannot.
+        gkey = ((ii[:, 1] & 0xF).astype(np.int64) << 12) | (((ii[:, 0] >> 8) & 0xFF).astype(np.int64) << 2) | \
+            ((ii[:, 0] >> 4) & 0x3).astype(np.int64)
+        _, ginv = np.unique(gkey, return_inverse=True)
+        gcnt = np.bincount(ginv)
+        gmean = np.bincount(ginv, weights=en) / gcnt
+        gmax = np.zeros(len(gcnt))
+        np.maximum.at(gmax, ginv, en)
+        ckey = gkey >> 2
+        _, cinv = np.unique(ckey, return_inverse=True)
+        cmean = np.bincount(cinv, weights=en) / np.bincount(cinv)
+        print(f"  groups (XCC, SE, CU, SIMD): {len(gcnt)}, waves per group {np.bincount(gcnt)[1:]}; launch end "
+              f"{span:.2f}; wave end p50 {np.median(en):.2f} mean {en.mean():.2f} max {en.max():.2f}; "
+              f"mean over groups of (group max - group mean) {np.mean(gmax - gmean):.2f}; group mean p50 "
+              f"{np.median(gmean):.2f} max {gmean.max():.2f}; CU mean p50 {np.median(cmean):.2f} max {cmean.max():.2f}")
+        late = int(np.argmax(gmax))
+        print(f"  the group of the last wave: ends {np.sort(en[ginv == late]).round(1).tolist()}, mean {gmean[late]:.2f}")

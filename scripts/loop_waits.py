@@ -100,6 +100,35 @@ def sequence(lines, lo, hi):
     return seq
 
 
+def static_counts(lines, lo, hi):
+    """--counts: the extent's static instruction mix, and its SGPR-spill lane moves
+    (v_readlane / v_writelane) by outermost source line"""
+    ops, where, chain = Counter(), Counter(), "?"
+    for i in range(lo, hi + 1):
+        t = lines[i].strip()
+        if LOC.match(t):
+            c = t.split(";", 1)[1] if ";" in t else ""
+            parts = [f"{f.rsplit('/', 1)[-1]}:{ln}" for f, ln in CHAIN.findall(c)]
+            chain = parts[-1] if parts else "line " + LOC.match(t).group(1)
+            continue
+        op = t.split(";")[0].strip()
+        if not op or op.startswith(".") or op.endswith(":"):
+            continue
+        mn = op.split()[0]
+        ops[mn] += 1
+        if mn in ("v_readlane_b32", "v_writelane_b32"):
+            where[chain + " " + mn[2:-4]] += 1
+    total = sum(ops.values())
+    br = sum(n for m, n in ops.items() if re.match(r"s_c?branch", m))
+    print(f"   static instructions {total}: v_readlane_b32 {ops['v_readlane_b32']}, v_writelane_b32 "
+          f"{ops['v_writelane_b32']}, s_nop {ops['s_nop']}, branches {br}, s_and_saveexec_b64 "
+          f"{ops['s_and_saveexec_b64']}, s_setprio {ops['s_setprio']}, s_waitcnt {ops['s_waitcnt']}, VALU (v_*) "
+          f"{sum(n for m, n in ops.items() if m.startswith('v_'))}, SALU (s_*) "
+          f"{sum(n for m, n in ops.items() if m.startswith('s_'))}")
+    for w, c in sorted(where.items(), key=lambda kv: -kv[1]):
+        print(f"     {c:3d}  {w}")
+
+
 def lgkm(op):
     """the lgkmcnt of a wait, or None when it does not wait on lgkmcnt"""
     m = re.search(r"lgkmcnt\((\d+)\)", op)
@@ -127,6 +156,7 @@ def main():
     ap.add_argument("asm")
     ap.add_argument("kernels", nargs="+")
     ap.add_argument("--summary", action="store_true", help="counts only")
+    ap.add_argument("--counts", action="store_true", help="also the loop's static instruction mix and spill lane moves")
     a = ap.parse_args()
     lines = open(a.asm).read().splitlines()
     for spec in a.kernels:
@@ -157,6 +187,8 @@ def main():
         print(f"   LDS instructions {n['L']} (reads {reads}), vector-memory {n['V']}, s_waitcnt {n['W']} "
               f"(lgkmcnt(0) {full}, counted lgkmcnt {counted})")
         print(f"   exposed LDS round trips: {len(exp)}")
+        if a.counts:
+            static_counts(lines, lo, hi)
         by = Counter(seq[i][2].split(" < ")[-1] + "  (" + seq[i][2].split(" < ")[0] + ")" for i in exp)
         for where, c in sorted(by.items(), key=lambda kv: (int(kv[0].split(":")[1].split()[0]), kv[0])):
             print(f"     {c:3d}  {where}")
