@@ -58,7 +58,8 @@ struct Params {
     uint8_t *term, *trunc;
     const int64_t *seeds;    // reset-only launches
     const uint8_t *mask;
-    uint32_t ablate;         // unused (ablations are the compile-time VN_ABLATE)
+    uint32_t box;            // every room of the set is an exact box (EnvLayout::box): vn_cubic::launch may pick the
+                             // BOX kernels, whose ray record is arithmetic (no kernel reads this field)
     int prio;                // step kernel: issue priority (bits, VnTuning::prio; default 67); vn_cubic::launch adds
                              // its own bits above them (window record, base level, bits 12..31 the launch's tag)
     int dflush;              // step kernel: a step's obs flush after the next step's load issue (VnTuning::dflush)
@@ -87,7 +88,7 @@ int ensure_mt(int device);
 // *wrec_written: whether the env's previous step launch wrote the window
 // records; updated for this launch (wrec_early: VnTuning::wrec_early)
 int launch(bool reset_only, int defer, int wrec_early, bool *wrec_written, const void *params, hipStream_t s);
-std::string label(bool reset_only, bool ext, bool fast, int defer, const void *params);
+std::string label(bool reset_only, bool ext, bool fast, int defer, const void *params, bool *box = nullptr);
 int export_state(const void *params, int64_t *out, hipStream_t s);
 int export_belief(const void *params, int8_t *out, int pw, int pd, hipStream_t s);
 int gae(const float *rew, const float *val, const float *starts, const float *last_v, const float *dones, int T, int N,

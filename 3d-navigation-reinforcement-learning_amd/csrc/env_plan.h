@@ -91,6 +91,7 @@ struct EnvLayout {
     int sline = 0;     // simpleEnv line layout (simple_line_kernel), rooms <= 32 x 32 x 8
     int defer = 0;     // CubicEnv byte-mark mode with deferred plane marks (PCM 3; rows <= 2 words)
     int pcache = 0;    // CubicEnv plane-set mode (PH 8, rooms <= 64 x 64): see pset_fill
+    int box = 0;       // CubicEnv: every room of the set is an exact box (rooms_box_exact; set by vn_create)
     uint32_t episode_bytes = (uint32_t)sizeof(EpisodeRec);   // both variants: the agent's episode record (own buffer)
 };
 
@@ -324,6 +325,57 @@ inline int build_room_tables(const VnRoomSet &rooms, const VnConfig &cfg, RoomTa
     out->maxD = maxD;
     out->maxH = maxH;
     return VN_OK;
+}
+
+// ----------------------------------------------------------------------------
+// Exact boxes: rooms whose ray records are arithmetic
+// ----------------------------------------------------------------------------
+// The ray record of free cell (x, y, z) of a W x D x H room that is one wall
+// layer around a free interior: every run ends at the opposite wall.  The BOX
+// step kernels (voxnav_env.hip) compute this instead of loading the record;
+// room_is_exact_box below holds it against the table, so both sides read the
+// one formula.
+VN_HD RayRec box_ray_rec(int W, int D, int H, int x, int y, int z) {
+    const uint32_t ex = (uint32_t)(W - 2 - x) | 0x80u, wx = (uint32_t)(x - 1) | 0x80u;
+    const uint32_t ey = (uint32_t)(D - 2 - y) | 0x80u, wy = (uint32_t)(y - 1) | 0x80u;
+    const uint32_t ez = (uint32_t)(H - 2 - z) | 0x80u, wz = (uint32_t)(z - 1) | 0x80u;
+    RayRec r;
+    r.x = ex | (wx << 8) | (ey << 16) | (wy << 24);
+    r.y = ez | (wz << 8);
+    return r;
+}
+
+// A room (its W * D * H records, build_room_tables' order) is an exact box when
+// the record of every free cell equals box_ray_rec, both words: the six runs
+// with their wall flags, and bits 16 / 17 clear.  The comparison is with what a
+// kernel would have loaded, cell by cell, not a second reading of the walls: a
+// pillar, a second wall layer, an opening in the shell or a run past 127 cells
+// each change some free cell's record.  (Wall cells are never stood in: no
+// kernel reads their runs.)
+inline bool room_is_exact_box(int W, int D, int H, const RayRec *rays) {
+    if (W < 3 || D < 3 || H < 3) return false;
+    for (int x = 0; x < W; ++x)
+        for (int y = 0; y < D; ++y)
+            for (int z = 0; z < H; ++z) {
+                const RayRec &t = rays[((size_t)x * D + y) * H + z];
+                if ((t.y >> 16) & 1u) continue;   // a wall cell
+                const RayRec f = box_ray_rec(W, D, H, x, y, z);
+                if (t.x != f.x || t.y != f.y) return false;
+            }
+    return true;
+}
+
+// ... and an env is box-exact when every room of its set is (EnvLayout::box)
+inline bool rooms_box_exact(const RoomTables &rt) {
+    const size_t nr = rt.desc.size() / 8;
+    if (nr == 0) return false;
+    for (size_t r = 0; r < nr; ++r) {
+        const uint32_t whd = rt.desc[8 * r], ray_off = rt.desc[8 * r + 2];
+        if (!room_is_exact_box((int)(whd & 0xff), (int)((whd >> 8) & 0xff), (int)((whd >> 16) & 0xff),
+                               rt.rays.data() + ray_off))
+            return false;
+    }
+    return true;
 }
 
 // LDS table (TAB_SIZE floats, then the simpleEnv rewards: TAB_ALL in all):

@@ -99,7 +99,8 @@ struct DeviceGuard {
 // changes it on a live env: scripts/ab_same.py); the caller sets its pointers.
 Params call_params(const VnEnv *e) {
     Params p = e->params;
-    p.prio = e->tuning.prio;       // bit 0: the step's load issue, 1: the obs flush, 6: base level (2: the rotation)
+    p.prio = e->tuning.prio;       // bit 0: the step's load issue, 1: the obs flush, 6: base level (2: the rotation),
+                                   // 3: a box-exact env's launches stay on the ray table
     p.dflush = e->tuning.dflush;   // bit 0: the deferred obs flush in the byte-mark kernels (PCM 3), bit 1: in the plane-set ones
     p.wrec_k = e->tuning.wrec_k;   // launches of at most this many steps write the window record
     return p;
@@ -115,7 +116,7 @@ int launch_env(bool reset_only, VnEnv *e, const Params &p, hipStream_t s) {
 // the defaults of every VnTuning field, here only (vn_tuning_default)
 constexpr VnTuning kTuningDefault = {/*pcache_cap*/ -1, /*defer*/ -1, /*simple_layout*/ 0, /*prio*/ 67,
                                      /*dflush*/ VN_DFLUSH_DEFAULT, /*wrec_k*/ VN_WREC_K_DEFAULT, /*wrec_early*/ 1};
-constexpr int PRIO_USER_BITS = 1 | 2 | 4 | 64;   // what env_kernel decodes of VnTuning::prio (vn_cubic::launch adds its own bits)
+constexpr int PRIO_USER_BITS = 1 | 2 | 4 | 8 | 64;   // what env_kernel and vn_cubic::launch decode of VnTuning::prio (launch adds its own bits)
 
 int check_tuning(const VnTuning &t) {
     if (t.pcache_cap < -1 || t.pcache_cap > 2)
@@ -265,6 +266,7 @@ Params env_params(const VnEnv *e, size_t belief_off) {
     p.sline = l.sline;
     p.wimg = e->wimg.as<const int8_t>();
     p.pcache = l.pcache;
+    p.box = (uint32_t)l.box;
     p.scratch = e->scratch.as<float>();
     p.stood = e->stood.as<uint32_t>();
     p.pnz = p.stood ? reinterpret_cast<uint2 *>(p.stood + (size_t)e->N * 32u) : nullptr;
@@ -422,6 +424,8 @@ int vn_create_tuned(const VnRoomSet *rooms, int32_t n_agents, const VnConfig *cf
     if (e->cfg.seed_stride == 0) e->cfg.seed_stride = n_agents;
     e->total_free = rt.total_free;
     e->lay = plan_layout(cfg->variant, cfg->local_map_length, rt.maxW, rt.maxD, rt.maxH, tun);
+    // every free cell's ray record held against the box formula: the step kernels may compute it (env_kernel's BOX)
+    e->lay.box = cfg->variant == VN_VARIANT_CUBIC && rooms_box_exact(rt) ? 1 : 0;
     size_t belief_off = 0;
     bool belief_contig = false;
 #ifdef VN_DIAG
@@ -548,6 +552,18 @@ int vn_kernel_label(const VnEnv *env, int32_t k_steps, int32_t explicit_actions,
                               : vn_cubic::label(reset_only, ext, fast != 0, l.defer, &p);
     std::snprintf(buf, (size_t)len, "%s", s.c_str());
     return (int)s.size() < len ? VN_OK : fail(VN_ERR_INVALID, "buffer too small (%d)", (int)len);
+}
+
+int vn_kernel_box(const VnEnv *env, int32_t k_steps, int32_t explicit_actions, int32_t fast, int32_t *box) {
+    if (!env || !box) return fail(VN_ERR_INVALID, "NULL argument");
+    bool b = false;
+    if (env->lay.variant != VN_VARIANT_SIMPLE) {
+        Params p = call_params(env);
+        p.K = k_steps;
+        (void)vn_cubic::label(k_steps == 0, explicit_actions != 0, fast != 0, env->lay.defer, &p, &b);
+    }
+    *box = b ? 1 : 0;
+    return VN_OK;
 }
 
 int vn_export_state(VnEnv *env, int64_t *state_out, void *stream) {

@@ -140,6 +140,7 @@ constexpr uint32_t kMoveDir = (2u << 0) | (0u << 2) | (3u << 4) | (1u << 6)     
 // between the two, plane-set kernels, launches of >= 8 steps: the number of
 // the SIMD's other waves that are ahead of this one, wave_progress below; with
 // bit 2 the open-loop rotation over the CU's blocks that it replaced), default 67.
+// (Bit 3 of the same field is no priority: PRIO_TABLE below, read by launch_ph alone.)
 // One runtime level dispatch per step (vn_setprio: the instruction takes an
 // immediate): after the issue section; the flush's level stays until the
 // next step's issue section raises it (a few instructions later).
@@ -147,6 +148,7 @@ constexpr int kPrioIssue = 3;   // while the step's move is computed and its loa
 constexpr int kPrioFlush = 2;   // while the obs flush's stores are issued
 // Params::prio bits the host sets (vn_cubic::launch), beside env_window.h's PRIO_WREC_*:
 constexpr int PRIO_ROTATE = 4;          // (user bit) the base level is the open-loop rotation
+constexpr int PRIO_TABLE = 8;           // (user bit, read by the host only) a box-exact env launches the table kernels
 constexpr int PRIO_BASE = 512;          // a base level applies: bit 6, a plane-set kernel, K >= 8
 constexpr int PRIO_TAG_SHIFT = 12;      // bits 12..31: the launch's tag in the progress table
 
@@ -261,12 +263,21 @@ __device__ __forceinline__ void wave_time_record(uint64_t rkern, uint64_t rend) 
 }
 #endif
 
-template <int PH, bool EXT, bool FAST, bool RESET_ONLY, int PCM, bool DFL = false>
+// BOX: the ray record computed from the agent's coordinates and its room's size
+// (box_ray_rec, env_plan.h) instead of loaded: one vector load (16 distinct
+// lines per wave instruction, L2 hits) less per step.  For envs whose every
+// room vn_create has proven an exact box against the table (EnvLayout::box);
+// plane-set step kernels only, without the deferred flush.  A separate
+// instantiation the host picks (launch_ph): no runtime test in the step loop,
+// and a general room's kernels are what they were.  DESIGN.md 7.20.
+template <int PH, bool EXT, bool FAST, bool RESET_ONLY, int PCM, bool DFL = false, bool BOX = false>
 __global__ __launch_bounds__((PCM == 1 || PCM == 2) ? VN_PC_BLOCK : BLOCK,
                              (PCM == 1 || PCM == 2) ? VN_PC_MIN_WAVES : VN_MIN_WAVES_PER_SIMD)
 void env_kernel(Params p) {
     constexpr bool PC = PCM == 1 || PCM == 2;   // plane-set mode
     constexpr bool DM = PCM == 3;                // byte-mark mode, deferred plane marks
+    static_assert(!BOX || (PC && !RESET_ONLY && !DFL), "BOX is for the plane-set step kernels, in-step flush");
+    constexpr bool ARITH_REC = BOX || (VN_ABLATE & 8192u);   // (8192: diagnostics, the BOX path forced on any room)
     using RT = typename std::conditional<PCM == 2, uint32_t, uint64_t>::type;
     constexpr int kAgents = (PC ? VN_PC_BLOCK : BLOCK) / GROUP;
     constexpr bool CW = PC || DM;     // obs staged as code words (STAGE_WORDS), expanded at the flush
@@ -431,7 +442,7 @@ void env_kernel(Params p) {
             // step 0's ray record depends on the state alone: issued ahead of
             // the fill, so a one-step launch waits for one load round trip
             // after the state instead of two
-            if (!(VN_ABLATE & 8192u)) {
+            if (!ARITH_REC) {
                 rec0 = p.rays[R.ray_off + (uint32_t)((gf.x * R.D + gf.y) * R.H + gf.z)];
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -566,12 +577,10 @@ void env_kernel(Params p) {
                 if (shifted) tile_shift_issue<PH, SB>(p, map, tile, dir, g.x, g.y, R, dirty, q, sl, st, g.room);
                 if (PC && shifted) pset_shift_issue<RT, SB>(p, map, ps, dir, g.x, g.y, R, pdirty, q, pl, st);
                 uint2 rec;
-                // diagnostics: the record computed for a walled box (exact for box rooms only)
-                if (VN_ABLATE & 8192u) {
-                    const uint32_t ex = (uint32_t)(R.W - 2 - g.x) | 0x80u, wx = (uint32_t)(g.x - 1) | 0x80u;
-                    const uint32_t ey = (uint32_t)(R.D - 2 - g.y) | 0x80u, wy = (uint32_t)(g.y - 1) | 0x80u;
-                    const uint32_t ez = (uint32_t)(R.H - 2 - g.z) | 0x80u, wz = (uint32_t)(g.z - 1) | 0x80u;
-                    rec = make_uint2(ex | (wx << 8) | (ey << 16) | (wy << 24), ez | (wz << 8));
+                // BOX: the record of an exact box, from the agent's own room's size (step 0's too)
+                if (ARITH_REC) {
+                    const RayRec b = box_ray_rec(R.W, R.D, R.H, g.x, g.y, g.z);
+                    rec = make_uint2(b.x, b.y);
                 } else if (k == 0) {
                     rec = rec0;
                 } else {
@@ -878,6 +887,13 @@ static bool use_dfl(int pcm, int N, int K, int dflush_bits) {
     return (pcm == 3) ? (dflush_bits & 1) != 0 : (dflush_bits & 2) != 0;
 }
 
+// The arithmetic ray record (env_kernel's BOX): step launches of a box-exact
+// env (Params::box, proven by vn_create) in the plane-set modes, unless the
+// call's VnTuning::prio bit 3 asks for the table kernels; the deferred-flush
+// instantiation stays on the table (the caller tests that).
+constexpr bool pcm_box_capable(int pcm) { return pcm == 1 || pcm == 2; }
+static bool use_box(int pcm, const Params &p) { return pcm_box_capable(pcm) && p.box && !(p.prio & PRIO_TABLE); }
+
 template <int PH, bool RESET_ONLY, int PCM>
 int launch_ph(int N, hipStream_t s, const Params &p) {
     const int bs = (PCM == 1 || PCM == 2) ? VN_PC_BLOCK : BLOCK;
@@ -888,8 +904,19 @@ int launch_ph(int N, hipStream_t s, const Params &p) {
     const bool fast = p.reward && p.term && p.trunc && !p.actions_out;
     constexpr bool CAP = pcm_dfl_capable(PCM);
     const bool dfl = CAP && !RESET_ONLY && use_dfl(PCM, N, p.K, p.dflush);
+    // (BCAP false: the names below are the table instantiations themselves)
+    constexpr bool BCAP = pcm_box_capable(PCM) && !RESET_ONLY;
+    const bool box = BCAP && use_box(PCM, p);
     if (RESET_ONLY)
         hipLaunchKernelGGL((env_kernel<PH, false, false, true, PCM>), grid, block, 0, s, p);
+    else if (box && p.actions && fast)
+        hipLaunchKernelGGL((env_kernel<PH, true, true, false, PCM, false, BCAP>), grid, block, 0, s, p);
+    else if (box && p.actions)
+        hipLaunchKernelGGL((env_kernel<PH, true, false, false, PCM, false, BCAP>), grid, block, 0, s, p);
+    else if (box && fast && !dfl)
+        hipLaunchKernelGGL((env_kernel<PH, false, true, false, PCM, false, BCAP>), grid, block, 0, s, p);
+    else if (box && !dfl)
+        hipLaunchKernelGGL((env_kernel<PH, false, false, false, PCM, false, BCAP>), grid, block, 0, s, p);
     else if (p.actions && fast)
         hipLaunchKernelGGL((env_kernel<PH, true, true, false, PCM>), grid, block, 0, s, p);
     else if (p.actions)
@@ -957,12 +984,15 @@ int launch(bool reset_only, int defer, int wrec_early, bool *wrec_written, const
 
 // The kernel instantiation launch picks for a call shape of p.K steps
 // (diagnostics / bench labels); kept next to launch so the two selections agree.
-std::string label(bool reset_only, bool ext, bool fast, int defer, const void *params) {
+// The name stops at the DFL argument; *box (when given): whether the call
+// launches that name's BOX instantiation (the ray record computed).
+std::string label(bool reset_only, bool ext, bool fast, int defer, const void *params, bool *box) {
     const Params &p = *static_cast<const Params *>(params);
     char buf[160];
     const int pcm = env_pcm(p.ph, p.pcache, defer);
     const bool x = !reset_only && ext, f = !reset_only && fast;
     const bool dfl = !reset_only && !x && use_dfl(pcm, p.N, p.K, p.dflush);
+    if (box) *box = !reset_only && !dfl && use_box(pcm, p);
     std::snprintf(buf, sizeof(buf), "env_kernel<%d, %s, %s, %s, %d%s>", p.ph, x ? "true" : "false",
                   f ? "true" : "false", reset_only ? "true" : "false", pcm, dfl ? ", true" : "");
     return buf;

@@ -91,6 +91,7 @@ _SIGS = {
     "vn_plan_frontier": (C.c_int, [P, P, P, P, P]),
     "vn_export_state": (C.c_int, [P, P, P]),
     "vn_kernel_label": (C.c_int, [P, C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_int32]),
+    "vn_kernel_box": (C.c_int, [P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "vn_export_belief": (C.c_int, [P, P, P]),
     "vn_import_state": (C.c_int, [P, P, P, P, P, P, P]),
     "vn_snapshot_tag": (C.c_int, [P, C.POINTER(C.c_uint64)]),

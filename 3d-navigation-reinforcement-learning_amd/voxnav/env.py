@@ -433,6 +433,15 @@ class BatchedGridEnv:
                                                buf, 160), "vn_kernel_label")
         return buf.value.decode()
 
+    def kernel_box(self, k_steps: int = 16, explicit_actions: bool = False, fast: bool = True) -> bool:
+        """Whether that call launches the label's BOX instantiation, which
+        computes the ray record of an exact box instead of loading it
+        (``vn_kernel_box``; tuning ``prio`` bit 8 keeps such an env on the table)."""
+        box = C.c_int32(0)
+        _native.check(self.lib.vn_kernel_box(self._h, int(k_steps), int(bool(explicit_actions)), int(bool(fast)),
+                                             C.byref(box)), "vn_kernel_box")
+        return bool(box.value)
+
     def export_state(self) -> torch.Tensor:
         out = torch.empty((self.num_agents, _native.VN_STATE_FIELDS), dtype=torch.int64, device=self.device)
         _native.check(self.lib.vn_export_state(self._h, _ptr(out), self._stream()), "vn_export_state")

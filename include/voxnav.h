@@ -121,8 +121,11 @@ typedef struct VnTuning {
                                 issue, 2 the obs flush, 64 a base level among the
                                 SIMD's waves in launches of >= 8 steps (the wave
                                 behind its mates goes first), 4 that level from the
-                                open-loop rotation over a CU's blocks instead;
-                                default 67                                         */
+                                open-loop rotation over a CU's blocks instead; and
+                                one bit that is no priority, 8: an env whose rooms
+                                are all exact boxes (vn_kernel_box) launches the
+                                kernels that load the ray record, not the ones that
+                                compute it (for paired timing); default 67         */
     int32_t dflush;          /* deferred obs flush (a step's flush after the next
                                 step's load issue; launches of more than one step),
                                 bits: 1 in the byte-mark kernels, 2 in the plane-set
@@ -138,7 +141,7 @@ typedef struct VnTuning {
 int vn_tuning_default(VnTuning *out);
 /* vn_create with a tuning (NULL = defaults).  VN_ERR_INVALID for a field out
  * of range: pcache_cap in {-1, 0, 1, 2}, defer in {-1, 0}, simple_layout in
- * {0, 1, 2}, prio a subset of bits 71, dflush in 0..3, wrec_k >= 0,
+ * {0, 1, 2}, prio a subset of bits 79, dflush in 0..3, wrec_k >= 0,
  * wrec_early in {0, 1}. */
 int vn_create_tuned(const VnRoomSet *rooms, int32_t n_agents, const VnConfig *cfg, int32_t device,
                     const VnTuning *tuning, VnEnv **out);
@@ -233,6 +236,17 @@ int vn_step_actions(VnEnv *env, const int32_t *actions, int32_t k_steps, float *
  */
 int vn_kernel_label(const VnEnv *env, int32_t k_steps, int32_t explicit_actions, int32_t fast, char *buf,
                     int32_t len);
+/*
+ * *box = 1 when a call of this shape launches the BOX instantiation of the
+ * kernel vn_kernel_label names (the label stops before that template
+ * argument): the step kernel that computes each ray record from the agent's
+ * coordinates and its room's size instead of loading it.  vn_create proves,
+ * cell by cell against the ray table, that every room of the set is a box of
+ * one wall layer around a free interior; such an env's plane-set step
+ * launches take it, unless VnTuning::prio bit 8 is set or the deferred flush
+ * is chosen.  Results are identical.  0 for every other env and call.
+ */
+int vn_kernel_box(const VnEnv *env, int32_t k_steps, int32_t explicit_actions, int32_t fast, int32_t *box);
 int vn_export_state(VnEnv *env, int64_t *state_out, void *stream);
 int vn_export_belief(VnEnv *env, int8_t *belief_out, void *stream);
 

@@ -73,7 +73,7 @@ def main():
     for k, v in res.items():
         v = sorted(v)
         print(json.dumps({"variant": k[0], "config": ":".join(k[1]), "Gsteps_median": round(v[len(v) // 2] / 1e9, 3),
-                          "Gsteps_max": round(v[-1] / 1e9, 3)}))
+                          "Gsteps_min": round(v[0] / 1e9, 3), "Gsteps_max": round(v[-1] / 1e9, 3)}), flush=True)
 
 
 if __name__ == "__main__":

@@ -6,7 +6,10 @@ per config one env; every round resets it (same seed) and times each
 setting in alternating order, so both settings run on the same memory
 (a fresh allocation alone moves the rate by 10-15 %, scripts/ab.py).
 --lib PATH runs the process on another build (_native.use_library).
-  python scripts/ab_same.py --var prio --values 67,66 --configs 65536:32x32x8:10:20"""
+  python scripts/ab_same.py --var prio --values 67,66 --configs 65536:32x32x8:10:20
+--var box_table is bit 8 of prio alone (over --prio): 0 a box-exact env's BOX
+kernels, which compute the ray record, 1 the kernels that load it
+  python scripts/ab_same.py --var box_table --values 0,1 --configs 65536:32x32x8:10:128"""
 import argparse
 import contextlib
 import json
@@ -31,6 +34,7 @@ def main():
     ap.add_argument("--steps", type=int, default=1024)
     ap.add_argument("--warmup", type=int, default=64)
     ap.add_argument("--rounds", type=int, default=9)
+    ap.add_argument("--prio", type=int, default=67, help="the other prio bits under --var box_table")
     ap.add_argument("--lib", default=None, help="another build of the library for this process")
     a = ap.parse_args()
     if a.lib:
@@ -49,6 +53,10 @@ def main():
             for v in (vals if r % 2 == 0 else vals[::-1]):
                 if a.var in _native.OPTIONS:
                     setting = _native.option(a.var, int(v))
+                elif a.var == "box_table":
+                    e.set_tuning(prio=(a.prio & ~8) | (8 if int(v) else 0))
+                    setting = contextlib.nullcontext()
+                    assert e.kernel_box(F) == (not int(v)), "the env is not box-exact"
                 else:
                     e.set_tuning(**{a.var: int(v)})
                     setting = contextlib.nullcontext()
