@@ -18,6 +18,7 @@ include/voxnav.h.  Public API:
   checkpoint.save_env_state / load_env_state   an env's agents (.npz: portable exports or a raw snapshot)
   branch.fan_out / branch.evaluate_plans   copies of chosen agents in a wider env; the returns of K-step action plans
   planner.FrontierExplorer / planner.evaluate_planner   the frontier-exploration baseline from the agents' belief maps
+  imitate.DaggerCollector / imitate.BCLearner / imitate.warm_start   DAgger warm start from the frontier planner
   sharding            multi-GPU agent sharding helpers
 """
 from . import rooms  # noqa: F401

@@ -570,6 +570,7 @@ class RolloutCollector:
         hbuf = csbuf and not self.fused
         for t in range(T):
             self._forward(self._obs[t], t, in_rollout=True)
+            self._choose_actions(t)
             self.env.step_into(self.actions[t], self._obs[t + 1], self.rewards[t], self._term, self._trunc,
                                self._tobs, reward64=self._r64)
             # after the step, in one launch: episode_starts[t+1], the Monitor, the
@@ -625,6 +626,12 @@ class RolloutCollector:
                              episode_starts=self._starts[:T], values=self.values, log_probs=self.log_probs,
                              advantages=adv, returns=ret, lstm_h=hs, lstm_c=cs, last_values=self._last_values,
                              dones=self._starts[T])
+
+    def _choose_actions(self, t: int) -> None:
+        """Hook between the policy's forward pass and the env step of rollout
+        step t: ``actions[t]`` holds the policy's sample and is what the env
+        executes.  Nothing to do here (voxnav.imitate.DaggerCollector mixes in
+        the planner's action)."""
 
     def _bootstrap(self, count: torch.Tensor):
         """V(terminal obs) from the stashed critic states, rewards[t, a] +=

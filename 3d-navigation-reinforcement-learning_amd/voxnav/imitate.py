@@ -1,0 +1,304 @@
+"""DAgger warm start: the frontier planner teaches the policy.
+
+The frontier planner (``voxnav.planner``, ``vn_plan_frontier``) finishes every
+evaluate episode without a bump; this module lets a policy learn from it
+before (or instead of) PPO, by dataset aggregation (Ross, Gordon & Bagnell,
+"A Reduction of Imitation Learning and Structured Prediction to No-Regret
+Online Learning", AISTATS 2011):
+
+* ``DaggerCollector``: a ``RolloutCollector`` whose policy runs in the loop --
+  so the LSTM states, values and returns of the buffer are the policy's own --
+  while the planner labels every visited state.  The executed action is the
+  planner's with probability ``beta``, else the policy's sample
+  (``vn_dagger_mix``, one launch per step, nothing crosses to the host).
+* ``BCLearner``: a ``PPOLearner`` whose loss is the cross-entropy to the
+  labels (+ the value MSE and the entropy bonus), through the fused kernel
+  ``learn_ops.bc_loss`` (csrc/voxnav_bc_loss.hip) on the GPU and torch
+  autograd elsewhere.  Minibatches, the LSTM re-run from the stored states,
+  the all-reduce, the clip and the Adam step are the parent's.
+* ``warm_start``: ``ppo.learn``'s loop over the two, with a beta schedule.
+
+The policy module is the one ``PPOLearner``, ``save_checkpoint`` and
+``evaluate_policy`` take: a warm start followed by ``ppo.learn`` needs no
+conversion.  CubicEnv variant only, rooms within the planner's 64 x 64 bound.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+from typing import Callable, Dict, List, Optional, Sequence, Union
+
+import numpy as np
+import torch
+
+from . import _native, learn_ops
+from .collector import RolloutBuffer, RolloutCollector, _p
+from .env import BatchedGridEnv
+from .planner import FrontierExplorer
+from .ppo import PPOLearner
+
+PLANNER_MAX_PAD = 64     # vn_plan_frontier's bound on the padded width and depth
+
+
+@dataclass
+class DaggerBuffer(RolloutBuffer):
+    """A ``RolloutBuffer`` plus the planner's labels, all [T, N] on the GPU.
+
+    ``actions`` are the executed actions (what the env stepped with and what
+    obs / rewards / returns follow from).  ``log_probs`` are the log-probs of
+    the policy's own sample ``policy_actions``, not of the executed action:
+    with beta > 0 this is NOT a PPO buffer (the importance ratio of
+    ``PPOLearner`` would pair an action with another action's old log-prob).
+    With beta = 0 the executed action is the policy's sample everywhere and
+    the ``RolloutBuffer`` fields equal a plain ``RolloutCollector``'s.
+
+    ``expert_actions`` / ``expert_dist``: the planner's action and distance
+    for the state each step acted on (dist = -1: its fallback, no target in
+    reach); ``label_weight``: 1 where dist != -1 (the sample is labelled);
+    ``took_expert``: 1 where the planner's action was executed;
+    ``policy_actions``: the policy's sample."""
+    expert_actions: Optional[torch.Tensor] = None
+    expert_dist: Optional[torch.Tensor] = None
+    label_weight: Optional[torch.Tensor] = None
+    took_expert: Optional[torch.Tensor] = None
+    policy_actions: Optional[torch.Tensor] = None
+
+
+def _check_beta(beta) -> float:
+    b = float(beta)
+    if not 0.0 <= b <= 1.0:
+        raise ValueError(f"beta must be in [0, 1], got {beta!r}")
+    return b
+
+
+class DaggerCollector(RolloutCollector):
+    """``collect()`` fills a ``DaggerBuffer``: the policy acts in the loop, the
+    planner ``expert`` labels every step, and the env executes the planner's
+    action with probability ``beta`` (where the planner found a target), else
+    the policy's sample.
+
+    The draw is the sampler's Philox word under the key ``mix_seed`` with the
+    counter (global agent id, global step): like the Categorical draw, it does
+    not depend on how the agents are sharded over envs."""
+
+    def __init__(self, env: BatchedGridEnv, policy, *args, expert: Optional[FrontierExplorer] = None,
+                 beta: float = 1.0, mix_seed: int = 4242, **kwargs):
+        if env.variant != _native.VN_VARIANT_CUBIC:
+            raise ValueError("DaggerCollector: the frontier planner needs the CubicEnv variant")
+        info = env.info
+        if info.pad_w > PLANNER_MAX_PAD or info.pad_d > PLANNER_MAX_PAD:
+            raise ValueError(f"DaggerCollector: the frontier planner takes padded rooms of at most {PLANNER_MAX_PAD} x "
+                             f"{PLANNER_MAX_PAD} (this env: {info.pad_w} x {info.pad_d})")
+        self.expert = expert if expert is not None else FrontierExplorer()
+        self.beta = _check_beta(beta)
+        self.mix_seed = int(mix_seed)
+        super().__init__(env, policy, *args, **kwargs)
+        T, N, dev = self.n_steps, self.N, self.device
+        self.expert_actions = torch.zeros((T, N), dtype=torch.int32, device=dev)
+        self.expert_dist = torch.full((T, N), -1, dtype=torch.int32, device=dev)
+        self.policy_actions = torch.zeros((T, N), dtype=torch.int32, device=dev)
+        self.label_weight = torch.zeros((T, N), dtype=torch.uint8, device=dev)
+        self.took_expert = torch.zeros((T, N), dtype=torch.uint8, device=dev)
+
+    def set_beta(self, beta: float) -> None:
+        """The probability of executing the planner's action, from the next ``collect()`` on."""
+        self.beta = _check_beta(beta)
+
+    def _choose_actions(self, t: int) -> None:
+        self.policy_actions[t].copy_(self.actions[t])
+        _, dist = self.expert.act(self.env, out=self.expert_actions[t], return_dist=True)
+        self.expert_dist[t].copy_(dist)
+        _native.check(self.lib.vn_dagger_mix(_p(self.policy_actions[t]), _p(self.expert_actions[t]),
+                                             _p(self.expert_dist[t]), self.N, C.c_double(self.beta),
+                                             C.c_uint64(self.mix_seed & (2 ** 64 - 1)), C.c_uint64(self.t_global),
+                                             self.env.agent_id_base, _p(self.actions[t]), _p(self.took_expert[t]),
+                                             _p(self.label_weight[t]), self._stream()), "vn_dagger_mix")
+
+    @torch.no_grad()
+    def collect(self) -> DaggerBuffer:
+        """One rollout of n_steps.  The returned buffer views the collector's
+        storage: it stays valid until the next ``collect()``."""
+        rb = super().collect()
+        return DaggerBuffer(**{k: getattr(rb, k) for k in rb.__dataclass_fields__},
+                            expert_actions=self.expert_actions, expert_dist=self.expert_dist,
+                            label_weight=self.label_weight, took_expert=self.took_expert,
+                            policy_actions=self.policy_actions)
+
+
+class BCLearner(PPOLearner):
+    """Behaviour cloning on a ``DaggerBuffer``: per minibatch
+        loss = CE(labelled samples) + ent_coef * (-mean H) + vf_coef * MSE(returns, values)
+    (the formula of include/voxnav.h vn_bc_loss), with the parent's
+    minibatch order, LSTM re-run, all-reduce, grad-norm clip and Adam step.
+    ``clip_range`` and ``normalize_advantage`` are unused.  With a process
+    group the ranks' gradients are averaged equally, although their labelled
+    counts may differ."""
+
+    def __init__(self, policy, learning_rate: float = 3e-4, n_epochs: int = 10, batch_size: int = 64,
+                 ent_coef: float = 0.0, vf_coef: float = 0.5, max_grad_norm: float = 0.5, seed: int = 0,
+                 process_group=None):
+        super().__init__(policy, learning_rate=learning_rate, n_epochs=n_epochs, batch_size=batch_size,
+                         ent_coef=ent_coef, vf_coef=vf_coef, max_grad_norm=max_grad_norm, seed=seed,
+                         process_group=process_group)
+        self.fused_updates = 0     # minibatches that went through learn_ops.bc_loss
+
+    @staticmethod
+    def _labels(buf):
+        lab = getattr(buf, "expert_actions", None)
+        if lab is None:
+            raise ValueError("BCLearner needs the buffer's expert_actions (a DaggerBuffer)")
+        w = getattr(buf, "label_weight", None)
+        return lab.reshape(-1), (None if w is None else w.reshape(-1))
+
+    def update(self, buf, idx: torch.Tensor, packed: Optional[dict] = None) -> torch.Tensor:
+        """One minibatch (env-major flat ids ``idx``): loss, backward,
+        (all-reduce), clip, Adam.  Returns the logged values as a device
+        tensor: cross-entropy, value loss, entropy loss, loss, accuracy,
+        labelled share, grad norm."""
+        if self.recurrent:
+            (lat_pi, lat_vf, lat_pair), src = self._evaluate_recurrent(buf, packed or self._pack_begin(buf, idx))
+        else:
+            (lat_pi, lat_vf, lat_pair), src = self._evaluate_ff(buf, idx)
+        labels, weight = self._labels(buf)
+        pol = self.policy
+        ex = pol.mlp_extractor
+        if lat_pi.is_cuda:
+            F = ex.latent_dim_pi
+            if F == ex.latent_dim_vf and learn_ops.ppo_loss_supported(pol.action_net, pol.value_net, F):
+                h = learn_ops.mlp_pair(ex.policy_net, ex.value_net, lat_pi, None if lat_vf is lat_pi else lat_vf,
+                                       x_pair=lat_pair, stacked=True)
+                if h is not None:
+                    return self._update_fused_bc(buf, h, src, labels, weight)
+        # torch's ops and autograd: the CPU path, and heads the fused kernel does not take
+        h_pi, h_vf = learn_ops.mlp_pair(ex.policy_net, ex.value_net, lat_pi, None if lat_vf is lat_pi else lat_vf,
+                                        x_pair=lat_pair)
+        logits = learn_ops.linear(h_pi, pol.action_net)
+        values = learn_ops.linear(h_vf, pol.value_net).flatten()
+        lab = labels[src].long()
+        w = torch.ones_like(values) if weight is None else (weight[src] != 0).to(values.dtype)
+        ret = buf.returns.reshape(-1)[src]
+        lp_all = torch.log_softmax(logits, dim=-1)
+        lp = lp_all.gather(1, lab.view(-1, 1)).flatten()
+        entropy = -(lp_all.exp() * lp_all).sum(-1)
+        n = w.sum()
+        den = torch.clamp(n, min=1.0)
+        bc = (w * -lp).sum() / den
+        value_loss = ((ret - values) ** 2).mean()
+        entropy_loss = -entropy.mean()
+        loss = bc + self.ent_coef * entropy_loss + self.vf_coef * value_loss
+        self.optimizer.zero_grad(set_to_none=True)
+        loss.backward()
+        if self.group is not None:
+            self._allreduce_grads()
+        gnorm = self._clip_step()
+        with torch.no_grad():
+            A = logits.shape[-1]
+            top = logits.max(-1, keepdim=True).values
+            ar = torch.arange(A, device=logits.device).expand_as(logits)
+            amax = torch.where(logits == top, ar, torch.full_like(ar, A)).min(-1).values   # ties: the lowest index
+            # counts are integers: their quotients in f64, as the kernel's
+            acc = (w.double() * (amax == lab).double()).sum() / den.double()
+            return torch.stack([bc.detach().double(), value_loss.detach().double(), entropy_loss.detach().double(),
+                                loss.detach().double(), acc, n.double() / w.numel(), gnorm.detach().double()])
+
+    def _update_fused_bc(self, buf, h: torch.Tensor, src: torch.Tensor, labels: torch.Tensor,
+                         weight: Optional[torch.Tensor]) -> torch.Tensor:
+        """``update`` from the MLP latents h [2, M, F] on: the heads, the loss
+        and its gradient in the fused kernel (learn_ops.bc_loss), the latents'
+        gradient backpropagated through the MLP and LSTM kernels, the head
+        gradients assigned; then (all-reduce), clip, Adam."""
+        pol = self.policy
+        dh, grads, stats = learn_ops.bc_loss(h, pol.action_net, pol.value_net, src, labels, weight,
+                                             buf.returns.reshape(-1), self.ent_coef, self.vf_coef)
+        self.fused_updates += 1
+        self.optimizer.zero_grad(set_to_none=True)
+        h.backward(dh)
+        for prm, g in zip((pol.action_net.weight, pol.action_net.bias, pol.value_net.weight, pol.value_net.bias),
+                          grads):
+            if prm.requires_grad:
+                prm.grad = g
+        if self.group is not None:
+            self._allreduce_grads()
+        gnorm = self._clip_step()
+        return torch.cat([stats, gnorm.detach().double().view(1)])
+
+    def train(self, buf, epoch_orders: Optional[Sequence] = None) -> Dict[str, float]:
+        """One ``train()`` over a ``DaggerBuffer`` (n_epochs passes).  Returns
+        the means over the minibatches of ``bc_loss`` (cross-entropy on the
+        labelled samples), ``value_loss``, ``entropy_loss``, ``loss``,
+        ``accuracy`` (labelled samples whose argmax is the label), ``labelled``
+        (their share), ``grad_norm``, and ``n_minibatches``, ``n_updates``."""
+        T, N = buf.actions.shape
+        total = T * N
+        dev = buf.actions.device
+        self._labels(buf)
+        if self.recurrent and (buf.lstm_h is None or buf.lstm_c is None):
+            raise ValueError("the recurrent learner needs the buffer's LSTM states (store_lstm_states=True)")
+        orders = list(epoch_orders) if epoch_orders is not None else self._orders(total)
+        acc = torch.zeros(7, dtype=torch.float64, device=dev)
+        n_mb = 0
+        self.policy.train()
+        for order in orders:
+            if self.recurrent:
+                perm = torch.roll(torch.arange(total, device=dev), -int(order))
+            else:
+                perm = torch.as_tensor(np.asarray(order), dtype=torch.int64, device=dev)
+            logs = self.update_many(buf, [perm[s:s + self.batch_size] for s in range(0, total, self.batch_size)],
+                                    windows=self.recurrent)
+            acc += logs.sum(0)
+            n_mb += logs.shape[0]
+        m = (acc / max(1, n_mb)).tolist()
+        return dict(bc_loss=m[0], value_loss=m[1], entropy_loss=m[2], loss=m[3], accuracy=m[4], labelled=m[5],
+                    grad_norm=m[6], n_minibatches=n_mb, n_updates=self.n_updates)
+
+
+def warm_start(collector: DaggerCollector, learner: BCLearner, total_timesteps: int,
+               beta: Union[float, Callable[[int], float]] = 1.0, callback=None) -> List[Dict[str, float]]:
+    """DAgger: alternate ``collector.collect()`` under ``beta`` and
+    ``learner.train()`` until ``total_timesteps`` env steps were collected,
+    pushing the updated weights into the collector after every update (the
+    loop and the callbacks of ``ppo.learn``).
+
+    ``beta``: the probability of executing the planner's action, a float or
+    ``callable(iteration) -> float`` with iteration 0, 1, ... (DAgger lets it
+    fall from 1, e.g. ``lambda i: 0.5 ** i``).
+
+    Returns the per-iteration rows: the train dict (``BCLearner.train``),
+    ``beta``, ``num_timesteps``, ``expert_share`` (the mean of
+    ``took_expert``), the Monitor and exploration keys ``ppo.learn`` reports
+    and the evaluation's ``eval/*`` keys when one ran."""
+    if collector.policy is not learner.policy:
+        raise ValueError("collector and learner must share the policy module")
+    cbs = [] if callback is None else (list(callback) if isinstance(callback, (list, tuple)) else [callback])
+    per_rollout = collector.n_steps * collector.N
+    done, it, history = 0, 0, []
+    while done < total_timesteps:
+        b = float(beta(it)) if callable(beta) else float(beta)
+        collector.set_beta(b)
+        buf = collector.collect()
+        done += per_rollout
+        it += 1
+        evals = {}
+        for cb in cbs:
+            if hasattr(cb, "on_rollout_end"):
+                evals.update(cb.on_rollout_end(learner.policy, done, collector.n_steps, learner.optimizer) or {})
+        st = learner.train(buf)
+        collector.sync_weights()
+        st["beta"] = b
+        st["num_timesteps"] = done
+        st["expert_share"] = float(buf.took_expert.float().mean())
+        mon = getattr(collector, "monitor", None)
+        if mon is not None and mon.ep_info_buffer:
+            st["ep_rew_mean"] = mon.ep_rew_mean()
+            st["ep_len_mean"] = mon.ep_len_mean()
+        if mon is not None and getattr(mon, "last_exploration", None):
+            st.update(mon.last_exploration)
+        st.update(evals)
+        history.append(st)
+        stop = False
+        for cb in cbs:
+            if not hasattr(cb, "on_rollout_end") and callable(cb) and cb(it, done, st) is False:
+                stop = True
+        if stop:
+            break
+    return history

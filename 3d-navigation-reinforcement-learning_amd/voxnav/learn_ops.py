@@ -251,6 +251,51 @@ def ppo_loss(h: torch.Tensor, action_net: torch.nn.Linear, value_net: torch.nn.L
     return dh, grads, stats
 
 
+def bc_loss(h: torch.Tensor, action_net: torch.nn.Linear, value_net: torch.nn.Linear, src: Optional[torch.Tensor],
+            labels: torch.Tensor, weight: Optional[torch.Tensor], returns: torch.Tensor, ent_coef: float,
+            vf_coef: float):
+    """The behaviour-cloning minibatch loss and its gradient
+    (csrc/voxnav_bc_loss.hip, the formula in include/voxnav.h vn_bc_loss):
+    cross-entropy to the expert's ``labels`` over the samples with
+    ``weight``, value MSE and entropy bonus over all of them, in two launches
+    (three with weights).
+
+    h [2, M, F]: the (actor, critic) latents; src [M] int64 (or None): the
+    samples' rows in the flat rollout buffers ``labels`` (int32), ``weight``
+    (uint8, or None: every sample labelled) and ``returns``.  Returns (dh
+    [2, M, F], (d action_net.weight, d action_net.bias, d value_net.weight,
+    d value_net.bias), stats f64 [6]: cross-entropy, value loss, entropy loss,
+    loss, accuracy, labelled share).  Nothing is differentiated here: the
+    caller backpropagates dh from h and assigns the head gradients."""
+    lib = _native.load()
+    _, M, F = h.shape
+    A = action_net.out_features
+    dev = h.device
+    if h.stride(2) != 1 or h.stride(1) != F:
+        raise ValueError("bc_loss: latents must be row-contiguous [2, M, F]")
+    for t, dt in ((labels, torch.int32), (weight, torch.uint8), (returns, torch.float32)):
+        if t is not None and (t.dtype != dt or not t.is_contiguous() or t.device != dev):
+            raise ValueError("bc_loss: buffers must be contiguous int32 labels / uint8 weights / f32 returns on the "
+                             "latents' device")
+    if src is not None and (src.dtype != torch.int64 or src.numel() != M or not src.is_contiguous()):
+        raise ValueError("bc_loss: src must be [M] contiguous int64")
+    npart, nspart = C.c_int64(), C.c_int64()
+    _native.check(lib.vn_bc_loss_part_floats(M, F, A, C.byref(npart), C.byref(nspart)), "vn_bc_loss_part_floats")
+    dh = torch.empty((2, M, F), dtype=torch.float32, device=dev)
+    gh = torch.empty(A * F + A + F + 1, dtype=torch.float32, device=dev)
+    dbl = torch.empty(6 + nspart.value, dtype=torch.float64, device=dev)
+    part = torch.empty(npart.value, dtype=torch.float32, device=dev)
+    stats = dbl[:6]
+    wa, ba = action_net.weight.detach(), action_net.bias.detach()
+    wv, bv = value_net.weight.detach(), value_net.bias.detach()
+    _native.check(lib.vn_bc_loss(_p(h[0]), _p(h[1]), F, _p(wa.contiguous()), _p(ba), _p(wv.contiguous()), _p(bv),
+                                 _p(src), _p(labels), _p(weight), _p(returns), M, F, A, float(ent_coef),
+                                 float(vf_coef), _p(dh[0]), _p(dh[1]), _p(gh), _p(stats), _p(part), _p(dbl[6:]),
+                                 _stream(dev)), "vn_bc_loss")
+    grads = (gh[:A * F].view(A, F), gh[A * F:A * F + A], gh[A * F + A:A * F + A + F].view(1, F), gh[-1:])
+    return dh, grads, stats
+
+
 def grad_norm_scale(params, max_norm: float, work: Optional[torch.Tensor] = None):
     """The total 2-norm of the parameters' gradients and the divisor that
     clips them to ``max_norm`` (csrc/voxnav_ppo_loss.hip vn_grad_norm): two

@@ -816,6 +816,58 @@ int vn_ppo_loss(const float *hp, const float *hv, int64_t ldh, const float *wa, 
                 float ent_coef, float vf_coef, int32_t normalize_advantage, float *dhp, float *dhv, float *grad_heads,
                 double *stats, double *adv_sums, float *part, double *spart, void *stream);
 
+/* Behaviour-cloning minibatch loss + its gradient to the MLP latents
+ * (csrc/voxnav_bc_loss.hip), the counterpart of vn_ppo_loss for the DAgger warm
+ * start: cross-entropy to the frontier planner's actions (vn_plan_frontier) on
+ * the labelled samples, the value MSE and the entropy bonus over all of them.
+ *   z = h_pi Wa^T + ba,  lp = log_softmax(z),  p = exp(lp),  H = -sum_j p_j lp_j,  v = h_vf wv + bv
+ *   n = sum_i w_i  (w_i in {0,1};  n = M without weights)
+ *   loss = (1/max(n,1)) sum_i w_i (-lp_i[a*_i])  -  ent_coef (1/M) sum_i H_i  +  vf_coef (1/M) sum_i (ret_i - v_i)^2
+ *   dz_ij = (w_i / max(n,1)) (p_ij - [j = a*_i]) + (ent_coef / M) p_ij (lp_ij + H_i)
+ *   dv_i  = 2 vf_coef (v_i - ret_i) / M
+ *   dh_pi = dz Wa,  dh_vf = dv wv,  dWa = dz^T h_pi,  dba = sum dz,  dwv,  dbv
+ * With n = 0 the cross-entropy term, its gradient and the accuracy are exactly
+ * 0; the other terms are unchanged.
+ *   hp, hv [M][F] (row stride ldh >= F): the actor / critic latents (F = 64..256, % 64)
+ *   wa [A][F], ba [A] (action_net, 1 <= A <= 8); wv [F], bv [1] (value_net)
+ *   src [M] (NULL: identity): the buffer rows of the samples; labels int32 (a*,
+ *   the expert's actions), weight uint8 (nonzero = labelled; NULL: all
+ *   labelled), returns f32: the rollout buffers, indexed by src
+ *   -> dhp, dhv [M][F] contiguous: dloss/dlatent; grad_heads [A F + A + F + 1]:
+ *      d action_net.weight, d action_net.bias, d value_net.weight, d value_net.bias;
+ *      stats [6] f64: cross-entropy, value loss, entropy loss (-mean H), loss,
+ *      accuracy (the share of labelled samples whose argmax_j z_j, the lowest j
+ *      on ties, equals a*), n / M.  part / spart: workspaces of the sizes
+ *      vn_bc_loss_part_floats returns (floats / doubles).
+ * Two launches without weights, three with (the labelled count, an exact
+ * integer sum that stays on the device); stream-ordered, no host
+ * synchronisation; two calls on the same inputs give the same bits.
+ * VN_ERR_INVALID, with nothing launched: a NULL pointer other than src and
+ * weight; M < 1; A outside 1..8; F outside 64..256 or no multiple of 64;
+ * ldh < F.  vn_bc_loss_part_floats: M, F or A < 1. */
+int vn_bc_loss_part_floats(int32_t M, int32_t F, int32_t A, int64_t *n_part, int64_t *n_spart);
+int vn_bc_loss(const float *hp, const float *hv, int64_t ldh, const float *wa, const float *ba, const float *wv,
+               const float *bv, const int64_t *src, const int32_t *labels, const uint8_t *weight,
+               const float *returns, int32_t M, int32_t F, int32_t A, float ent_coef, float vf_coef, float *dhp,
+               float *dhv, float *grad_heads, double *stats, float *part, double *spart, void *stream);
+
+/* DAgger's executed action for one collector step (csrc/voxnav_bc_loss.hip):
+ * per agent i of N, with the planner's proposal expert[i] / dist[i]
+ * (vn_plan_frontier) and the policy's own sample policy[i],
+ *   u24 = word 0 of Philox4x32-10 >> 8, key mix_seed, counter (global agent id
+ *         agent_id_base + i, t_global | 2^63): the sampler's draw under another key
+ *   thr = floor(beta 2^24), computed on the host in double
+ *   took_expert[i]  = dist[i] != -1 and u24 < thr
+ *   executed[i]     = took_expert[i] ? expert[i] : policy[i]
+ *   label_weight[i] = dist[i] != -1
+ * Where the planner has only its fallback to offer (dist = -1) the policy acts
+ * and the sample carries no label.  executed may be the policy array itself.
+ * One launch, stream-ordered.  VN_ERR_INVALID, with nothing launched: a NULL
+ * pointer; N < 1; beta outside [0, 1] (a NaN included). */
+int vn_dagger_mix(const int32_t *policy, const int32_t *expert, const int32_t *dist, int32_t N, double beta,
+                  uint64_t mix_seed, uint64_t t_global, int64_t agent_id_base, int32_t *executed, uint8_t *took_expert,
+                  uint8_t *label_weight, void *stream);
+
 /* The total 2-norm of the parameter gradients (count <= 64 f32 tensors; device
  * pointers and element counts passed by host arrays) and the divisor the
  * fused Adam step applies to them: max(1, (norm + 1e-6) / max_norm), i.e.

@@ -1,0 +1,85 @@
+#!/usr/bin/env python3
+"""What a DAgger warm start buys: ``voxnav.imitate.warm_start`` on a training room
+set, then train/evaluate_grid.py's results table on an evaluate set for the warm-started policy,
+the same policy untrained, and the frontier planner that taught it (the row of DESIGN.md 10.3).
+
+The policy is the reference's (``--policy lstm``: RecurrentActorCriticPolicy, LSTM 256, pi / vf
+[256, 256, 128]; ``mlp``: ActorCriticPolicy with the same MLP).  beta falls linearly from 1 by
+--beta-step per iteration down to --beta-min.  --episodes agents per evaluation, agent i reset with
+seed + i, one deterministic episode each, L 10.  Prints the per-iteration rows, the table and one
+JSON line.  Needs a GPU."""
+import argparse
+import json
+import sys
+import time
+from pathlib import Path
+
+REPO = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(REPO / "3d-navigation-reinforcement-learning_amd"))
+import torch  # noqa: E402
+
+from voxnav.env import BatchedGridEnv  # noqa: E402
+from voxnav.evaluate import RESULTS_HEADER, evaluate_policy, results_table_row  # noqa: E402
+from voxnav.imitate import BCLearner, DaggerCollector, warm_start  # noqa: E402
+from voxnav.planner import evaluate_planner  # noqa: E402
+from voxnav.policy import ActorCriticPolicy, RecurrentActorCriticPolicy  # noqa: E402
+from voxnav.rooms import load_archive_set  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--train-set", default="P1_training")
+    ap.add_argument("--eval-set", default="P1_evaluate")
+    ap.add_argument("--policy", choices=["lstm", "mlp"], default="lstm")
+    ap.add_argument("--agents", type=int, default=512)
+    ap.add_argument("--n-steps", type=int, default=128)
+    ap.add_argument("--iterations", type=int, default=24)
+    ap.add_argument("--epochs", type=int, default=4)
+    ap.add_argument("--batch", type=int, default=8192)
+    ap.add_argument("--lr", type=float, default=3e-4)
+    ap.add_argument("--vf-coef", type=float, default=0.5)
+    ap.add_argument("--beta-step", type=float, default=0.05)
+    ap.add_argument("--beta-min", type=float, default=0.2)
+    ap.add_argument("--episodes", type=int, default=10)
+    ap.add_argument("--L", type=int, default=10)
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("warm_start_eval.py needs a GPU")
+    dev = "cuda:0"
+    torch.manual_seed(args.seed)
+    pol = (RecurrentActorCriticPolicy() if args.policy == "lstm" else ActorCriticPolicy()).to(dev)
+    eval_rooms = load_archive_set(args.eval_set)
+    kw = dict(n_episodes=args.episodes, local_map_length=args.L, seed=args.seed, device=dev)
+    rows = {"untrained policy": evaluate_policy(pol, eval_rooms, **kw)}
+
+    env = BatchedGridEnv(num_agents=args.agents, rooms=load_archive_set(args.train_set), local_map_length=args.L,
+                         device=dev)
+    col = DaggerCollector(env, pol, n_steps=args.n_steps)
+    ln = BCLearner(pol, learning_rate=args.lr, n_epochs=args.epochs, batch_size=args.batch, vf_coef=args.vf_coef,
+                   seed=args.seed)
+    t0 = time.time()
+
+    def show(it, done, st):
+        keys = ("beta", "expert_share", "labelled", "bc_loss", "accuracy", "value_loss", "grad_norm", "ep_finished_rate",
+                "ep_bumps_mean", "ep_coverage")
+        print(f"iter {it:3d} steps {done:9d} " + " ".join(f"{k}={st[k]:.4g}" for k in keys if k in st), flush=True)
+
+    hist = warm_start(col, ln, total_timesteps=args.iterations * args.agents * args.n_steps,
+                      beta=lambda i: max(args.beta_min, 1.0 - args.beta_step * i), callback=show)
+    torch.cuda.synchronize()
+    train_s = time.time() - t0
+    env.close()
+    rows["warm-started policy"] = evaluate_policy(pol, eval_rooms, **kw)
+    rows["frontier planner"] = evaluate_planner(eval_rooms, **kw)
+    print(f"warm start: {len(hist)} iterations, {hist[-1]['num_timesteps']} env steps, {train_s:.1f} s "
+          f"(fused loss minibatches: {ln.fused_updates} of {ln.n_updates})")
+    print(RESULTS_HEADER)
+    for label, r in rows.items():
+        print(results_table_row(f"{args.eval_set}: {label}", r))
+    print(json.dumps(dict(args=vars(args), train_seconds=train_s, history=hist,
+                          table={k: {a: b for a, b in r.items() if a != "episodes"} for k, r in rows.items()})))
+
+
+if __name__ == "__main__":
+    main()
