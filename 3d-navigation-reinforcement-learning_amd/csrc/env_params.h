@@ -125,6 +125,9 @@ int copy_agents(const void *dst, const void *src, const void *parts, const int32
 // caller has checked).  One launch; reads the env, writes actions / dist only.
 namespace vn_plan {
 int frontier(const void *params, const uint8_t *mask, int32_t *actions, int32_t *dist, int pw, int pd, hipStream_t s);
+// vn_plan_frontier_dists: also the per-action distances [N][6] and the set of best actions (u8 [N])
+int frontier_dists(const void *params, const uint8_t *mask, int32_t *actions, int32_t *dist, int32_t *dists,
+                   uint8_t *best, int pw, int pd, hipStream_t s);
 }  // namespace vn_plan
 
 // The simpleEnv unit (voxnav_simple.hip).

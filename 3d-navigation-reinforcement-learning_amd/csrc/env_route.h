@@ -8,12 +8,14 @@
 //   target  passable cells whose value is 0
 // This header holds the action -> direction table (do_action,
 // envs/CubicEnv.py:135-153), one breadth-first flood step on the rows, the
-// test of the agent's six neighbour cells, the pick and the fallback.  Plain
+// test of the agent's six neighbour cells, the pick and the fallback, and the
+// same search carried on until each of the six neighbours has its own distance
+// (vn_plan_frontier_dists).  Plain
 // C++17 with no HIP include (like env_plan.h / env_state.h): every function is
 // VN_HD, the loops take (tid, nth), and the block's barrier and vote come in
 // as a small object, so that the planning kernel (voxnav_plan.hip, one wave
-// per agent) and the stand-alone host driver (tests/host/route_check.cpp, one
-// thread, under the sanitizers) run the same code.  Anonymous namespace: one
+// per agent) and the stand-alone host drivers (tests/host/route_check.cpp and
+// route_dists_check.cpp, one thread, under the sanitizers) run the same code.  Anonymous namespace: one
 // copy per unit.
 #pragma once
 
@@ -148,6 +150,62 @@ VN_HD void rt_search(const Blk &blk, const uint64_t *pass, uint64_t *ra, uint64_
     }
     *action = rt_fallback(nv);
     *dist = -1;
+}
+
+// ---- the per-action distances (vn_plan_frontier_dists) ----
+constexpr int RT_UNREACHED = -1;   // n_k is passable and the flood never contained it
+constexpr int RT_BLOCKED = -2;     // n_k is not passable
+
+// The search for all six actions, on the same rows and buffers as rt_search:
+// dists[k] = j + 1 with j the smallest index such that n_k is in R_j,
+// RT_UNREACHED where the flood stopped growing (or ran `cap` steps) before it
+// contained the passable n_k, RT_BLOCKED where n_k is not passable (nv[k] < 0).
+// It ends as soon as every passable neighbour has its distance.  The barriers
+// follow rt_search's rule: every exit depends on values all threads hold
+// alike.  dists is the caller's own array of RT_ACTIONS; the loops over it
+// have constant bounds (unrolled, its entries stay in registers).
+template <class Blk>
+VN_HD void rt_search_all(const Blk &blk, const uint64_t *pass, uint64_t *ra, uint64_t *rb, const RtGeom &g, int x,
+                         int y, int z, int f, const int *nv, int cap, int tid, int nth, int *dists) {
+    blk.sync();                                   // pass, R_0 and nv are written
+    uint32_t want = 0u;
+#pragma unroll
+    for (int k = 0; k < RT_ACTIONS; ++k) {
+        dists[k] = nv[k] >= 0 ? RT_UNREACHED : RT_BLOCKED;
+        want |= nv[k] >= 0 ? 1u << k : 0u;
+    }
+    uint64_t *cur = ra, *nxt = rb;
+    for (int j = 0;; ++j) {
+        const uint32_t hit = rt_neighbours_in(cur, g, x, y, z, f) & want;   // R_j grows: a neighbour's first j
+#pragma unroll
+        for (int k = 0; k < RT_ACTIONS; ++k)
+            if ((hit >> k) & 1u) dists[k] = j + 1;
+        want &= ~hit;
+        if (!want || j >= cap) break;
+        if (!blk.any(rt_flood_pass(pass, cur, nxt, g, tid, nth))) break;
+        uint64_t *t = cur;
+        cur = nxt;
+        nxt = t;
+    }
+}
+
+// the smallest positive entry of dists, or -1 when none is positive
+VN_HD int rt_min_dist(const int *dists) {
+    int m = -1;
+#pragma unroll
+    for (int k = 0; k < RT_ACTIONS; ++k)
+        if (dists[k] > 0 && (m < 0 || dists[k] < m)) m = dists[k];
+    return m;
+}
+
+// best: bit k is set iff dists[k] is positive and the smallest positive entry
+VN_HD uint32_t rt_best_set(const int *dists) {
+    const int m = rt_min_dist(dists);
+    uint32_t b = 0u;
+#pragma unroll
+    for (int k = 0; k < RT_ACTIONS; ++k)
+        if (m > 0 && dists[k] == m) b |= 1u << k;
+    return b;
 }
 
 }  // namespace

@@ -691,6 +691,20 @@ int vn_plan_frontier(VnEnv *env, const uint8_t *mask, int32_t *actions, int32_t 
     return vn_plan::frontier(&p, mask, actions, dist, env->lay.pw, env->lay.pd, (hipStream_t)stream);
 }
 
+int vn_plan_frontier_dists(VnEnv *env, const uint8_t *mask, int32_t *actions, int32_t *dist, int32_t *dists,
+                           uint8_t *best, void *stream) {
+    if (!env || !dists) return fail(VN_ERR_INVALID, "NULL argument");
+    if (env->lay.variant == VN_VARIANT_SIMPLE)
+        return fail(VN_ERR_INVALID, "vn_plan_frontier_dists: the simpleEnv variant has no frontier planner (CubicEnv "
+                                    "only)");
+    if (env->lay.pw > 64 || env->lay.pd > 64)
+        return fail(VN_ERR_INVALID, "vn_plan_frontier_dists: padded room %d x %d is wider or deeper than 64 (one "
+                                    "64-bit row over x per (y, z))", env->lay.pw, env->lay.pd);
+    DeviceGuard dg(env->device);
+    const Params p = call_params(env);
+    return vn_plan::frontier_dists(&p, mask, actions, dist, dists, best, env->lay.pw, env->lay.pd, (hipStream_t)stream);
+}
+
 #ifdef VN_DIAG
 // diagnostics build (placement study): the device address of the belief maps and the per-agent stride
 int vn_debug_belief_addr(const VnEnv *env, uint64_t *addr, uint32_t *stride) {

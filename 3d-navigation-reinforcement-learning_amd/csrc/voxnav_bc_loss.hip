@@ -1,6 +1,7 @@
-// voxnav_bc_loss.hip -- the DAgger warm start's two kernels (f32): the
+// voxnav_bc_loss.hip -- the DAgger warm start's kernels (f32): the
 // behaviour-cloning minibatch loss with its gradient down to the MLP latents
-// (vn_bc_loss, the counterpart of vn_ppo_loss in voxnav_ppo_loss.hip), and the
+// (vn_bc_loss, the counterpart of vn_ppo_loss in voxnav_ppo_loss.hip; and
+// vn_bc_loss_set, the same on sets of labels), and the
 // per-step choice between the planner's action and the policy's own
 // (vn_dagger_mix).
 //
@@ -21,6 +22,14 @@
 // lanes by xor butterflies, the action weights in LDS, per-block partials of
 // the head gradients (f32) and of the logged sums (f64); (3) the partials
 // summed in a fixed order, so two calls on the same inputs give the same bits.
+//
+// vn_bc_loss_set is the same call with a set of equally good actions per
+// sample (a uint8 bit set) in place of the label:
+//   S = set & (2^A - 1);  labelled iff S != 0 and w != 0
+//   ce = logsumexp_j z_j - logsumexp_{j in S} z_j,  q = softmax of z restricted to S
+//   dz_ij = (w_i / max(n,1)) (p_ij - q_ij) + the entropy term above
+// through bc_loss_kernel<.., SET = true>; its labelled count depends on the
+// sets, so launch (1) always runs (bc_count_set_kernel).
 //
 // All LDS is in the dynamic region and every carve offset is a multiple of
 // 16 B: the float4 reads of the action weights and the float4 stores of the
@@ -83,6 +92,29 @@ __global__ __launch_bounds__(256) void bc_count_kernel(const uint8_t *__restrict
     if (t == 0) cnt[blockIdx.x] = s[0];
 }
 
+// the same for label sets: a sample counts when its set has a bit below A (and its weight, if any, is nonzero)
+__global__ __launch_bounds__(256) void bc_count_set_kernel(const uint8_t *__restrict__ set,
+                                                           const uint8_t *__restrict__ wgt,
+                                                           const int64_t *__restrict__ src, int M, uint32_t amask,
+                                                           int64_t *__restrict__ cnt) {
+    __shared__ int s[256];
+    const int t = threadIdx.x;
+    const int per = (M + kCntBlocks - 1) / kCntBlocks;
+    const int i0 = blockIdx.x * per, i1 = min(M, i0 + per);
+    int c = 0;
+    for (int i = i0 + t; i < i1; i += 256) {
+        const int64_t r = src ? src[i] : i;
+        c += ((set[r] & amask) != 0u && (wgt == nullptr || wgt[r] != 0)) ? 1 : 0;
+    }
+    s[t] = c;
+    __syncthreads();
+    for (int h = 128; h >= 1; h >>= 1) {
+        if (t < h) s[t] += s[t + h];
+        __syncthreads();
+    }
+    if (t == 0) cnt[blockIdx.x] = s[0];
+}
+
 // the labelled count n of the minibatch (M without weights)
 __device__ __forceinline__ int64_t labelled(const int64_t *cnt, bool weighted, int M) {
     if (!weighted) return M;
@@ -106,7 +138,12 @@ __device__ __forceinline__ int head_slot(int i, int A, int F) {
 // 64 q + 4 (l & 15) .. +3 (q < Q) -- one float4 per q, 256 B contiguous per
 // group; the wave's 4 groups take 4 samples at once.  AM: A rounded up to
 // even (the per-action registers); the action weights are read from LDS.
-template <int Q, int AM>
+//
+// SET (vn_bc_loss_set): g.lab points at the samples' label sets, one uint8
+// each, instead of int32 labels (BcArgs and with it vn_bc_loss' kernels stay
+// as they were); the target of the cross-entropy is the softmax restricted to
+// the set, and a sample with an empty set is unlabelled.
+template <int Q, int AM, bool SET>
 __global__ __launch_bounds__(256) void bc_loss_kernel(BcArgs g) {
     // action weights [AM][F], then the waves' head-gradient rows [kWaves][PGP],
     // then the waves' f64 sums [kWaves][kStats]
@@ -128,7 +165,7 @@ __global__ __launch_bounds__(256) void bc_loss_kernel(BcArgs g) {
     const float bv = g.bv[0];
     // 1 / max(n, 1) with n the labelled count (every thread folds the same 64
     // integers; the loads are uniform over the block)
-    const int64_t n_lab = labelled(g.cnt, g.wgt != nullptr, g.M);
+    const int64_t n_lab = labelled(g.cnt, SET || g.wgt != nullptr, g.M);
     const float inv_l = 1.0f / (float)(n_lab > 0 ? n_lab : 1);
     const float inv_n = 1.0f / (float)g.M;
     __syncthreads();
@@ -176,9 +213,13 @@ __global__ __launch_bounds__(256) void bc_loss_kernel(BcArgs g) {
         // keep the LDS weight reads inside the loop (hoisted, they would hold
         // A Q float4 registers for the whole kernel)
         asm volatile("" ::: "memory");
-        const int lab = g.lab[r];
+        int lab = 0;
+        uint32_t S = 0u;                      // the label set, bits below A
+        if constexpr (SET) S = (uint32_t)reinterpret_cast<const uint8_t *>(g.lab)[r] & ((1u << A) - 1u);
+        else lab = g.lab[r];
         const float ret = g.ret[r];
-        const bool has = g.wgt ? g.wgt[r] != 0 : true;
+        bool has = g.wgt ? g.wgt[r] != 0 : true;
+        if constexpr (SET) has = has && S != 0u;
         float z[AM];
 #pragma unroll
         for (int a = 0; a < AM; ++a) {
@@ -210,9 +251,28 @@ __global__ __launch_bounds__(256) void bc_loss_kernel(BcArgs g) {
             p[a] = a < A ? expf(lpa[a]) : 0.0f;
             ent -= a < A ? p[a] * lpa[a] : 0.0f;
         }
-        float lp = 0.0f;
+        // lp: the log-probability of the label, or of the whole set; q: the target distribution
+        float lp = 0.0f, q[SET ? AM : 1];
+        bool hit = false;
+        if constexpr (SET) {
+            // logsumexp over S around S's own maximum: a set far below the top logit keeps its digits
+            float zs = -INFINITY, ses = 0.0f;
 #pragma unroll
-        for (int a = 0; a < AM; ++a) lp = a == lab ? lpa[a] : lp;
+            for (int a = 0; a < AM; ++a) zs = ((S >> a) & 1u) ? fmaxf(zs, z[a]) : zs;
+#pragma unroll
+            for (int a = 0; a < AM; ++a) {
+                q[a] = ((S >> a) & 1u) ? expf(z[a] - zs) : 0.0f;
+                ses += q[a];
+            }
+            const float inv_s = S != 0u ? 1.0f / ses : 0.0f;
+#pragma unroll
+            for (int a = 0; a < AM; ++a) q[a] *= inv_s;
+            lp = S != 0u ? (zs + logf(ses)) - (zmax + lse) : 0.0f;
+            hit = ((S >> amax) & 1u) != 0u;
+        } else {
+#pragma unroll
+            for (int a = 0; a < AM; ++a) lp = a == lab ? lpa[a] : lp;
+        }
         const float w = ok ? 1.0f : 0.0f;     // a padding pass contributes nothing
         const float gce = (has && ok) ? inv_l : 0.0f;
         const float gent = g.ent_coef * inv_n * w;
@@ -223,7 +283,9 @@ __global__ __launch_bounds__(256) void bc_loss_kernel(BcArgs g) {
 #pragma unroll
         for (int a = 0; a < AM; ++a) {
             if (a >= A) break;
-            const float dz = gce * (p[a] - (a == lab ? 1.0f : 0.0f)) + gent * p[a] * (lpa[a] + ent);
+            float dz;
+            if constexpr (SET) dz = gce * (p[a] - q[a]) + gent * p[a] * (lpa[a] + ent);
+            else dz = gce * (p[a] - (a == lab ? 1.0f : 0.0f)) + gent * p[a] * (lpa[a] + ent);
             gba[a] += dz;
 #pragma unroll
             for (int q = 0; q < Q; ++q) {
@@ -244,7 +306,8 @@ __global__ __launch_bounds__(256) void bc_loss_kernel(BcArgs g) {
                 st[0] += has ? (double)(-lp) : 0.0;
                 st[1] += (double)((ret - v) * (ret - v));
                 st[2] += (double)ent;
-                st[3] += (has && amax == lab) ? 1.0 : 0.0;
+                if constexpr (SET) st[3] += (has && hit) ? 1.0 : 0.0;
+                else st[3] += (has && amax == lab) ? 1.0 : 0.0;
             }
         }
 #pragma unroll
@@ -376,6 +439,64 @@ __global__ __launch_bounds__(256) void dagger_mix_kernel(const int32_t *policy, 
     took[i] = tk ? 1 : 0;
     weight[i] = lab ? 1 : 0;
 }
+// vn_bc_loss (labels) and vn_bc_loss_set (label_set): exactly one of the two is given
+int bc_launch(const float *hp, const float *hv, int64_t ldh, const float *wa, const float *ba, const float *wv,
+              const float *bv, const int64_t *src, const int32_t *labels, const uint8_t *label_set,
+              const uint8_t *weight, const float *returns, int32_t M, int32_t F, int32_t A, float ent_coef,
+              float vf_coef, float *dhp, float *dhv, float *grad_heads, double *stats, float *part, double *spart,
+              void *stream) {
+    const bool set = label_set != nullptr;
+    if (!hp || !hv || !wa || !ba || !wv || !bv || (!labels && !label_set) || !returns || !dhp || !dhv || !grad_heads ||
+        !stats || !part || !spart)
+        return fail(VN_ERR_INVALID, "NULL argument");
+    if (M < 1 || A < 1 || A > kMaxA) return fail(VN_ERR_INVALID, "bad sizes M=%d A=%d (A <= %d)", M, A, kMaxA);
+    if (F < 64 || F > 256 || F % 64) return fail(VN_ERR_INVALID, "latent width F=%d: a multiple of 64 up to 256", F);
+    if (ldh < F) return fail(VN_ERR_INVALID, "latent row stride %lld < F", (long long)ldh);
+    const hipStream_t s = (hipStream_t)stream;
+    const int nb = (M + kWaves * kSPW - 1) / (kWaves * kSPW);
+    // the labelled counts sit behind the blocks' sums in spart (8-byte words both)
+    int64_t *cnt = reinterpret_cast<int64_t *>(spart + (int64_t)nb * kStats);
+    // (a set may be empty, so the labelled count of the set form depends on the sets: always counted)
+    if (set)
+        hipLaunchKernelGGL(bc_count_set_kernel, dim3(kCntBlocks), dim3(256), 0, s, label_set, weight, src, M,
+                           (1u << A) - 1u, cnt);
+    else if (weight)
+        hipLaunchKernelGGL(bc_count_kernel, dim3(kCntBlocks), dim3(256), 0, s, weight, src, M, cnt);
+    BcArgs g{};
+    g.hp = hp; g.hv = hv; g.ldh = ldh; g.wa = wa; g.ba = ba; g.wv = wv; g.bv = bv;
+    g.src = src; g.wgt = weight; g.ret = returns; g.cnt = cnt;
+    g.lab = set ? reinterpret_cast<const int32_t *>(label_set) : labels;   // (bc_loss_kernel, SET)
+    g.dhp = dhp; g.dhv = dhv; g.part = part; g.spart = spart;
+    g.M = M; g.F = F; g.A = A; g.ent_coef = ent_coef; g.vf_coef = vf_coef;
+    const int PG = A * F + A + F + 1;
+    const int PGP = (PG + 3) & ~3;
+    const int AM = (A + 1) / 2 * 2;
+    const size_t lds = ((size_t)AM * F + (size_t)kWaves * PGP) * sizeof(float) + (size_t)kWaves * kStats * sizeof(double);
+#define VN_BC_K(Q_, AM_)                                                                               \
+    if (set) hipLaunchKernelGGL((bc_loss_kernel<Q_, AM_, true>), dim3(nb), dim3(256), lds, s, g);      \
+    else hipLaunchKernelGGL((bc_loss_kernel<Q_, AM_, false>), dim3(nb), dim3(256), lds, s, g);         \
+    break;
+#define VN_BC_Q(Q_)                                                                                    \
+    switch (AM) {                                                                                      \
+        case 2: VN_BC_K(Q_, 2)                                                                         \
+        case 4: VN_BC_K(Q_, 4)                                                                         \
+        case 6: VN_BC_K(Q_, 6)                                                                         \
+        default: VN_BC_K(Q_, 8)                                                                        \
+    }
+    switch (F / 64) {
+        case 1: VN_BC_Q(1) break;
+        case 2: VN_BC_Q(2) break;
+        case 3: VN_BC_Q(3) break;
+        default: VN_BC_Q(4) break;
+    }
+#undef VN_BC_Q
+#undef VN_BC_K
+    hipLaunchKernelGGL(bc_loss_reduce_kernel, dim3((unsigned)((PG + 63) / 64 + 1)), dim3(256), 0, s, part, spart, cnt,
+                       (set || weight) ? 1 : 0, nb, PG, M, ent_coef, vf_coef, grad_heads, stats);
+    VN_HIP(hipGetLastError());
+    return VN_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -392,44 +513,16 @@ int vn_bc_loss(const float *hp, const float *hv, int64_t ldh, const float *wa, c
                const float *bv, const int64_t *src, const int32_t *labels, const uint8_t *weight,
                const float *returns, int32_t M, int32_t F, int32_t A, float ent_coef, float vf_coef, float *dhp,
                float *dhv, float *grad_heads, double *stats, float *part, double *spart, void *stream) {
-    if (!hp || !hv || !wa || !ba || !wv || !bv || !labels || !returns || !dhp || !dhv || !grad_heads || !stats ||
-        !part || !spart)
-        return fail(VN_ERR_INVALID, "NULL argument");
-    if (M < 1 || A < 1 || A > kMaxA) return fail(VN_ERR_INVALID, "bad sizes M=%d A=%d (A <= %d)", M, A, kMaxA);
-    if (F < 64 || F > 256 || F % 64) return fail(VN_ERR_INVALID, "latent width F=%d: a multiple of 64 up to 256", F);
-    if (ldh < F) return fail(VN_ERR_INVALID, "latent row stride %lld < F", (long long)ldh);
-    const hipStream_t s = (hipStream_t)stream;
-    const int nb = (M + kWaves * kSPW - 1) / (kWaves * kSPW);
-    // the labelled counts sit behind the blocks' sums in spart (8-byte words both)
-    int64_t *cnt = reinterpret_cast<int64_t *>(spart + (int64_t)nb * kStats);
-    if (weight) hipLaunchKernelGGL(bc_count_kernel, dim3(kCntBlocks), dim3(256), 0, s, weight, src, M, cnt);
-    BcArgs g{};
-    g.hp = hp; g.hv = hv; g.ldh = ldh; g.wa = wa; g.ba = ba; g.wv = wv; g.bv = bv;
-    g.src = src; g.lab = labels; g.wgt = weight; g.ret = returns; g.cnt = cnt;
-    g.dhp = dhp; g.dhv = dhv; g.part = part; g.spart = spart;
-    g.M = M; g.F = F; g.A = A; g.ent_coef = ent_coef; g.vf_coef = vf_coef;
-    const int PG = A * F + A + F + 1;
-    const int PGP = (PG + 3) & ~3;
-    const int AM = (A + 1) / 2 * 2;
-    const size_t lds = ((size_t)AM * F + (size_t)kWaves * PGP) * sizeof(float) + (size_t)kWaves * kStats * sizeof(double);
-#define VN_BC_Q(Q_)                                                                                    \
-    switch (AM) {                                                                                      \
-        case 2: hipLaunchKernelGGL((bc_loss_kernel<Q_, 2>), dim3(nb), dim3(256), lds, s, g); break;    \
-        case 4: hipLaunchKernelGGL((bc_loss_kernel<Q_, 4>), dim3(nb), dim3(256), lds, s, g); break;    \
-        case 6: hipLaunchKernelGGL((bc_loss_kernel<Q_, 6>), dim3(nb), dim3(256), lds, s, g); break;    \
-        default: hipLaunchKernelGGL((bc_loss_kernel<Q_, 8>), dim3(nb), dim3(256), lds, s, g); break;   \
-    }
-    switch (F / 64) {
-        case 1: VN_BC_Q(1) break;
-        case 2: VN_BC_Q(2) break;
-        case 3: VN_BC_Q(3) break;
-        default: VN_BC_Q(4) break;
-    }
-#undef VN_BC_Q
-    hipLaunchKernelGGL(bc_loss_reduce_kernel, dim3((unsigned)((PG + 63) / 64 + 1)), dim3(256), 0, s, part, spart, cnt,
-                       weight ? 1 : 0, nb, PG, M, ent_coef, vf_coef, grad_heads, stats);
-    VN_HIP(hipGetLastError());
-    return VN_OK;
+    return bc_launch(hp, hv, ldh, wa, ba, wv, bv, src, labels, nullptr, weight, returns, M, F, A, ent_coef, vf_coef,
+                     dhp, dhv, grad_heads, stats, part, spart, stream);
+}
+
+int vn_bc_loss_set(const float *hp, const float *hv, int64_t ldh, const float *wa, const float *ba, const float *wv,
+                   const float *bv, const int64_t *src, const uint8_t *label_set, const uint8_t *weight,
+                   const float *returns, int32_t M, int32_t F, int32_t A, float ent_coef, float vf_coef, float *dhp,
+                   float *dhv, float *grad_heads, double *stats, float *part, double *spart, void *stream) {
+    return bc_launch(hp, hv, ldh, wa, ba, wv, bv, src, nullptr, label_set, weight, returns, M, F, A, ent_coef,
+                     vf_coef, dhp, dhv, grad_heads, stats, part, spart, stream);
 }
 
 int vn_dagger_mix(const int32_t *policy, const int32_t *expert, const int32_t *dist, int32_t N, double beta,

@@ -89,6 +89,7 @@ _SIGS = {
     "vn_step_actions": (C.c_int, [P, P, C.c_int32, P, P, P, P, P, P, P]),
     "vn_copy_agents": (C.c_int, [P, P, P, P, P, P]),
     "vn_plan_frontier": (C.c_int, [P, P, P, P, P]),
+    "vn_plan_frontier_dists": (C.c_int, [P, P, P, P, P, P, P]),
     "vn_export_state": (C.c_int, [P, P, P]),
     "vn_kernel_label": (C.c_int, [P, C.c_int32, C.c_int32, C.c_int32, C.c_char_p, C.c_int32]),
     "vn_kernel_box": (C.c_int, [P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
@@ -142,6 +143,8 @@ _SIGS = {
     "vn_bc_loss_part_floats": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, P, P]),
     "vn_bc_loss": (C.c_int, [P, P, C.c_int64, P, P, P, P, P, P, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                              C.c_float, P, P, P, P, P, P, P]),
+    "vn_bc_loss_set": (C.c_int, [P, P, C.c_int64, P, P, P, P, P, P, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_float,
+                                 C.c_float, P, P, P, P, P, P, P]),
     "vn_dagger_mix": (C.c_int, [P, P, P, C.c_int32, C.c_double, C.c_uint64, C.c_uint64, C.c_int64, P, P, P, P]),
     "vn_grad_norm": (C.c_int, [P, P, C.c_int32, C.c_float, P, P, P, P]),
     "vn_adam_step": (C.c_int, [P, P, P, P, P, P, C.c_int32, P, P, C.c_float, C.c_float, C.c_float, C.c_float,

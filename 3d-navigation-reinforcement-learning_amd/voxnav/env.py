@@ -49,6 +49,14 @@ class Rollout(NamedTuple):
     terminal_obs: Optional[torch.Tensor] = None  # f32 [K, N, obs_dim] (step_actions): rows valid where an episode ended
 
 
+class FrontierDists(NamedTuple):
+    """``BatchedGridEnv.plan_frontier_dists``: the planner's action and, per first action, its distance."""
+    actions: torch.Tensor        # i32 [N]: plan_frontier's action
+    dist: torch.Tensor           # i32 [N]: plan_frontier's dist (-1: the fallback)
+    dists: torch.Tensor          # i32 [N, 6]: steps to the nearest target through action k; -1 unreached, -2 not passable
+    best: torch.Tensor           # u8 [N]: bit k set iff dists[:, k] is the smallest positive entry
+
+
 class EnvSnapshot(NamedTuple):
     """A whole-env raw snapshot (``BatchedGridEnv.snapshot``): opaque,
     layout-native bytes that only an env with the same tag can load."""
@@ -387,6 +395,40 @@ class BatchedGridEnv:
         _native.check(self.lib.vn_plan_frontier(self._h, _ptr(m), _ptr(out), _ptr(dist), self._stream()),
                       "vn_plan_frontier")
         return (out, dist) if return_dist else out
+
+    def plan_frontier_dists(self, mask: Optional[torch.Tensor] = None, out: Optional["FrontierDists"] = None):
+        """The frontier planner's distance for each first action
+        (``vn_plan_frontier_dists``; the rule is in include/voxnav.h).  Returns
+        the named tuple ``(actions, dist, dists, best)``: ``actions`` / ``dist``
+        int32 [N] exactly as ``plan_frontier`` gives them; ``dists`` int32
+        [N, 6], per action the steps to the nearest target when the first step
+        is that action, -1 where its cell is passable but reaches none, -2
+        where it is not passable; ``best`` uint8 [N], bit k set where action k
+        is among the shortest (0: the planner has only its fallback).  ``out``:
+        a ``FrontierDists`` of contiguous tensors to write into; rows of agents
+        without ``mask[i]`` are left as they were (in fresh tensors: action 0,
+        dist -1, dists -2, best 0).  Reads the env only; stream-ordered."""
+        if not self._was_reset:
+            raise RuntimeError("call reset() before plan_frontier_dists()")
+        N, dev = self.num_agents, self.device
+        if out is None:
+            out = FrontierDists(torch.zeros(N, dtype=torch.int32, device=dev),
+                                torch.full((N,), -1, dtype=torch.int32, device=dev),
+                                torch.full((N, 6), -2, dtype=torch.int32, device=dev),
+                                torch.zeros(N, dtype=torch.uint8, device=dev))
+        else:
+            out = FrontierDists(*out)
+            for name, t, dt, shape in (("actions", out.actions, torch.int32, (N,)), ("dist", out.dist, torch.int32, (N,)),
+                                       ("dists", out.dists, torch.int32, (N, 6)), ("best", out.best, torch.uint8, (N,))):
+                if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+                    raise ValueError(f"out.{name}: expected contiguous {dt} {shape} on {dev}")
+        m = None
+        if mask is not None:
+            m = torch.as_tensor(mask).to(device=dev, dtype=torch.uint8).reshape(N).contiguous()
+        _native.check(self.lib.vn_plan_frontier_dists(self._h, _ptr(m), _ptr(out.actions), _ptr(out.dist),
+                                                      _ptr(out.dists), _ptr(out.best), self._stream()),
+                      "vn_plan_frontier_dists")
+        return out
 
     def _check_rollout(self, out: Rollout, K: int, reward_f64: bool):
         """A caller-owned [K, N, ...] rollout chunk: the kernel writes all K

@@ -33,7 +33,7 @@ import torch
 
 from . import _native, learn_ops
 from .collector import RolloutBuffer, RolloutCollector, _p
-from .env import BatchedGridEnv
+from .env import BatchedGridEnv, FrontierDists
 from .planner import FrontierExplorer
 from .ppo import PPOLearner
 
@@ -56,12 +56,25 @@ class DaggerBuffer(RolloutBuffer):
     for the state each step acted on (dist = -1: its fallback, no target in
     reach); ``label_weight``: 1 where dist != -1 (the sample is labelled);
     ``took_expert``: 1 where the planner's action was executed;
-    ``policy_actions``: the policy's sample."""
+    ``policy_actions``: the policy's sample.
+
+    A collector with ``labels="set"`` also fills ``expert_dists`` ([T, N, 6]
+    int32: the planner's distance through each first action, -1 unreached, -2
+    not passable) and ``expert_set`` ([T, N] uint8: bit k set where action k
+    is among the shortest; 0 where dist = -1); both are None otherwise."""
     expert_actions: Optional[torch.Tensor] = None
     expert_dist: Optional[torch.Tensor] = None
     label_weight: Optional[torch.Tensor] = None
     took_expert: Optional[torch.Tensor] = None
     policy_actions: Optional[torch.Tensor] = None
+    expert_dists: Optional[torch.Tensor] = None
+    expert_set: Optional[torch.Tensor] = None
+
+
+def _check_labels(labels) -> str:
+    if labels not in ("action", "set"):
+        raise ValueError(f"labels must be 'action' or 'set', got {labels!r}")
+    return labels
 
 
 def _check_beta(beta) -> float:
@@ -79,10 +92,16 @@ class DaggerCollector(RolloutCollector):
 
     The draw is the sampler's Philox word under the key ``mix_seed`` with the
     counter (global agent id, global step): like the Categorical draw, it does
-    not depend on how the agents are sharded over envs."""
+    not depend on how the agents are sharded over envs.
+
+    ``labels="set"``: the planner is asked for the distance through every
+    first action (one ``plan_frontier_dists`` call per step in place of
+    ``plan_frontier``) and the buffer carries ``expert_dists`` and
+    ``expert_set`` as well.  The executed action does not change: the
+    planner's lowest-k action with probability ``beta``."""
 
     def __init__(self, env: BatchedGridEnv, policy, *args, expert: Optional[FrontierExplorer] = None,
-                 beta: float = 1.0, mix_seed: int = 4242, **kwargs):
+                 beta: float = 1.0, mix_seed: int = 4242, labels: str = "action", **kwargs):
         if env.variant != _native.VN_VARIANT_CUBIC:
             raise ValueError("DaggerCollector: the frontier planner needs the CubicEnv variant")
         info = env.info
@@ -92,6 +111,7 @@ class DaggerCollector(RolloutCollector):
         self.expert = expert if expert is not None else FrontierExplorer()
         self.beta = _check_beta(beta)
         self.mix_seed = int(mix_seed)
+        self.labels = _check_labels(labels)
         super().__init__(env, policy, *args, **kwargs)
         T, N, dev = self.n_steps, self.N, self.device
         self.expert_actions = torch.zeros((T, N), dtype=torch.int32, device=dev)
@@ -99,6 +119,10 @@ class DaggerCollector(RolloutCollector):
         self.policy_actions = torch.zeros((T, N), dtype=torch.int32, device=dev)
         self.label_weight = torch.zeros((T, N), dtype=torch.uint8, device=dev)
         self.took_expert = torch.zeros((T, N), dtype=torch.uint8, device=dev)
+        self.expert_dists = self.expert_set = None
+        if self.labels == "set":
+            self.expert_dists = torch.full((T, N, 6), -2, dtype=torch.int32, device=dev)
+            self.expert_set = torch.zeros((T, N), dtype=torch.uint8, device=dev)
 
     def set_beta(self, beta: float) -> None:
         """The probability of executing the planner's action, from the next ``collect()`` on."""
@@ -106,8 +130,12 @@ class DaggerCollector(RolloutCollector):
 
     def _choose_actions(self, t: int) -> None:
         self.policy_actions[t].copy_(self.actions[t])
-        _, dist = self.expert.act(self.env, out=self.expert_actions[t], return_dist=True)
-        self.expert_dist[t].copy_(dist)
+        if self.labels == "set":
+            self.expert.act_dists(self.env, out=FrontierDists(self.expert_actions[t], self.expert_dist[t],
+                                                              self.expert_dists[t], self.expert_set[t]))
+        else:
+            _, dist = self.expert.act(self.env, out=self.expert_actions[t], return_dist=True)
+            self.expert_dist[t].copy_(dist)
         _native.check(self.lib.vn_dagger_mix(_p(self.policy_actions[t]), _p(self.expert_actions[t]),
                                              _p(self.expert_dist[t]), self.N, C.c_double(self.beta),
                                              C.c_uint64(self.mix_seed & (2 ** 64 - 1)), C.c_uint64(self.t_global),
@@ -122,7 +150,8 @@ class DaggerCollector(RolloutCollector):
         return DaggerBuffer(**{k: getattr(rb, k) for k in rb.__dataclass_fields__},
                             expert_actions=self.expert_actions, expert_dist=self.expert_dist,
                             label_weight=self.label_weight, took_expert=self.took_expert,
-                            policy_actions=self.policy_actions)
+                            policy_actions=self.policy_actions, expert_dists=self.expert_dists,
+                            expert_set=self.expert_set)
 
 
 class BCLearner(PPOLearner):
@@ -132,21 +161,34 @@ class BCLearner(PPOLearner):
     minibatch order, LSTM re-run, all-reduce, grad-norm clip and Adam step.
     ``clip_range`` and ``normalize_advantage`` are unused.  With a process
     group the ranks' gradients are averaged equally, although their labelled
-    counts may differ."""
+    counts may differ.
+
+    ``labels="set"``: the labels are the buffer's ``expert_set`` (a
+    ``DaggerCollector(labels="set")``), the cross-entropy is -log of the
+    probability of the whole set of equally short actions (the formula of
+    vn_bc_loss_set, through ``learn_ops.bc_loss_set`` on the GPU), a sample
+    with an empty set is unlabelled, and ``accuracy`` counts the argmax lying
+    in the set."""
 
     def __init__(self, policy, learning_rate: float = 3e-4, n_epochs: int = 10, batch_size: int = 64,
                  ent_coef: float = 0.0, vf_coef: float = 0.5, max_grad_norm: float = 0.5, seed: int = 0,
-                 process_group=None):
+                 process_group=None, labels: str = "action"):
         super().__init__(policy, learning_rate=learning_rate, n_epochs=n_epochs, batch_size=batch_size,
                          ent_coef=ent_coef, vf_coef=vf_coef, max_grad_norm=max_grad_norm, seed=seed,
                          process_group=process_group)
-        self.fused_updates = 0     # minibatches that went through learn_ops.bc_loss
+        self.fused_updates = 0     # minibatches that went through learn_ops.bc_loss / bc_loss_set
+        self.labels = _check_labels(labels)
 
-    @staticmethod
-    def _labels(buf):
-        lab = getattr(buf, "expert_actions", None)
-        if lab is None:
-            raise ValueError("BCLearner needs the buffer's expert_actions (a DaggerBuffer)")
+    def _labels(self, buf):
+        if self.labels == "set":
+            lab = getattr(buf, "expert_set", None)
+            if lab is None:
+                raise ValueError("BCLearner(labels='set') needs the buffer's expert_set (a DaggerCollector with "
+                                 "labels='set')")
+        else:
+            lab = getattr(buf, "expert_actions", None)
+            if lab is None:
+                raise ValueError("BCLearner needs the buffer's expert_actions (a DaggerBuffer)")
         w = getattr(buf, "label_weight", None)
         return lab.reshape(-1), (None if w is None else w.reshape(-1))
 
@@ -174,11 +216,21 @@ class BCLearner(PPOLearner):
                                         x_pair=lat_pair)
         logits = learn_ops.linear(h_pi, pol.action_net)
         values = learn_ops.linear(h_vf, pol.value_net).flatten()
-        lab = labels[src].long()
+        A = logits.shape[-1]
         w = torch.ones_like(values) if weight is None else (weight[src] != 0).to(values.dtype)
         ret = buf.returns.reshape(-1)[src]
         lp_all = torch.log_softmax(logits, dim=-1)
-        lp = lp_all.gather(1, lab.view(-1, 1)).flatten()
+        if self.labels == "set":
+            # in_set [M, A]: bit j of the sample's set; -log sum_{j in S} p_j = lse(z) - lse(z over S)
+            in_set = ((labels[src].long().view(-1, 1) >> torch.arange(A, device=logits.device)) & 1).bool()
+            some = in_set.any(-1)
+            w = w * some.to(w.dtype)
+            masked = logits.masked_fill(~in_set, float("-inf"))
+            masked = torch.where(some.view(-1, 1), masked, torch.zeros_like(masked))   # (an empty set: no -inf row)
+            lp = torch.logsumexp(masked, dim=-1) - torch.logsumexp(logits, dim=-1)
+        else:
+            lab = labels[src].long()
+            lp = lp_all.gather(1, lab.view(-1, 1)).flatten()
         entropy = -(lp_all.exp() * lp_all).sum(-1)
         n = w.sum()
         den = torch.clamp(n, min=1.0)
@@ -192,12 +244,12 @@ class BCLearner(PPOLearner):
             self._allreduce_grads()
         gnorm = self._clip_step()
         with torch.no_grad():
-            A = logits.shape[-1]
             top = logits.max(-1, keepdim=True).values
             ar = torch.arange(A, device=logits.device).expand_as(logits)
             amax = torch.where(logits == top, ar, torch.full_like(ar, A)).min(-1).values   # ties: the lowest index
             # counts are integers: their quotients in f64, as the kernel's
-            acc = (w.double() * (amax == lab).double()).sum() / den.double()
+            right = in_set.gather(1, amax.view(-1, 1)).flatten() if self.labels == "set" else amax == lab
+            acc = (w.double() * right.double()).sum() / den.double()
             return torch.stack([bc.detach().double(), value_loss.detach().double(), entropy_loss.detach().double(),
                                 loss.detach().double(), acc, n.double() / w.numel(), gnorm.detach().double()])
 
@@ -208,8 +260,9 @@ class BCLearner(PPOLearner):
         gradient backpropagated through the MLP and LSTM kernels, the head
         gradients assigned; then (all-reduce), clip, Adam."""
         pol = self.policy
-        dh, grads, stats = learn_ops.bc_loss(h, pol.action_net, pol.value_net, src, labels, weight,
-                                             buf.returns.reshape(-1), self.ent_coef, self.vf_coef)
+        fused = learn_ops.bc_loss_set if self.labels == "set" else learn_ops.bc_loss
+        dh, grads, stats = fused(h, pol.action_net, pol.value_net, src, labels, weight, buf.returns.reshape(-1),
+                                 self.ent_coef, self.vf_coef)
         self.fused_updates += 1
         self.optimizer.zero_grad(set_to_none=True)
         h.backward(dh)

@@ -296,6 +296,45 @@ def bc_loss(h: torch.Tensor, action_net: torch.nn.Linear, value_net: torch.nn.Li
     return dh, grads, stats
 
 
+def bc_loss_set(h: torch.Tensor, action_net: torch.nn.Linear, value_net: torch.nn.Linear, src: Optional[torch.Tensor],
+                label_set: torch.Tensor, weight: Optional[torch.Tensor], returns: torch.Tensor, ent_coef: float,
+                vf_coef: float):
+    """``bc_loss`` with a set of equally good actions per sample
+    (``vn_bc_loss_set``, include/voxnav.h): ``label_set`` uint8, bit j set
+    where action j is optimal (the ``best`` of ``plan_frontier_dists``); the
+    cross-entropy is -log of the probability of the whole set, its gradient
+    p - softmax restricted to the set; a sample with an empty set is
+    unlabelled.  Everything else -- arguments, outputs, stats -- as ``bc_loss``
+    (accuracy: the argmax lies in the set).  Three launches."""
+    lib = _native.load()
+    _, M, F = h.shape
+    A = action_net.out_features
+    dev = h.device
+    if h.stride(2) != 1 or h.stride(1) != F:
+        raise ValueError("bc_loss_set: latents must be row-contiguous [2, M, F]")
+    for t, dt in ((label_set, torch.uint8), (weight, torch.uint8), (returns, torch.float32)):
+        if t is not None and (t.dtype != dt or not t.is_contiguous() or t.device != dev):
+            raise ValueError("bc_loss_set: buffers must be contiguous uint8 label sets / uint8 weights / f32 returns "
+                             "on the latents' device")
+    if src is not None and (src.dtype != torch.int64 or src.numel() != M or not src.is_contiguous()):
+        raise ValueError("bc_loss_set: src must be [M] contiguous int64")
+    npart, nspart = C.c_int64(), C.c_int64()
+    _native.check(lib.vn_bc_loss_part_floats(M, F, A, C.byref(npart), C.byref(nspart)), "vn_bc_loss_part_floats")
+    dh = torch.empty((2, M, F), dtype=torch.float32, device=dev)
+    gh = torch.empty(A * F + A + F + 1, dtype=torch.float32, device=dev)
+    dbl = torch.empty(6 + nspart.value, dtype=torch.float64, device=dev)
+    part = torch.empty(npart.value, dtype=torch.float32, device=dev)
+    stats = dbl[:6]
+    wa, ba = action_net.weight.detach(), action_net.bias.detach()
+    wv, bv = value_net.weight.detach(), value_net.bias.detach()
+    _native.check(lib.vn_bc_loss_set(_p(h[0]), _p(h[1]), F, _p(wa.contiguous()), _p(ba), _p(wv.contiguous()), _p(bv),
+                                     _p(src), _p(label_set), _p(weight), _p(returns), M, F, A, float(ent_coef),
+                                     float(vf_coef), _p(dh[0]), _p(dh[1]), _p(gh), _p(stats), _p(part), _p(dbl[6:]),
+                                     _stream(dev)), "vn_bc_loss_set")
+    grads = (gh[:A * F].view(A, F), gh[A * F:A * F + A], gh[A * F + A:A * F + A + F].view(1, F), gh[-1:])
+    return dh, grads, stats
+
+
 def grad_norm_scale(params, max_norm: float, work: Optional[torch.Tensor] = None):
     """The total 2-norm of the parameters' gradients and the divisor that
     clips them to ``max_norm`` (csrc/voxnav_ppo_loss.hip vn_grad_norm): two

@@ -6,6 +6,9 @@ a shortest known-free path to the nearest cell the agent knows to be free and
 has not visited.  This module wraps it in what the learned policies have:
 
 * ``FrontierExplorer.act(env)``: the actions of one step;
+* ``FrontierExplorer.act_dists(env)``: the same with the distance through each
+  of the six first actions and the set of equally short ones
+  (``vn_plan_frontier_dists``);
 * ``FrontierExplorer.rollout(env, k_steps)``: plan + step for k steps into
   [K, N] tensors -- the obs acted on, the actions, rewards and flags: a
   demonstration set for a warm start;
@@ -22,7 +25,7 @@ from typing import Dict, List, NamedTuple, Optional
 
 import torch
 
-from .env import BatchedGridEnv
+from .env import BatchedGridEnv, FrontierDists
 
 
 class PlannedRollout(NamedTuple):
@@ -43,6 +46,13 @@ class FrontierExplorer:
             return_dist: bool = False):
         """Actions int32 [N] for the env's current state (``plan_frontier``)."""
         return env.plan_frontier(mask=mask, out=out, return_dist=return_dist)
+
+    def act_dists(self, env: BatchedGridEnv, mask: Optional[torch.Tensor] = None, out: Optional[FrontierDists] = None):
+        """``(actions, dist, dists, best)`` for the env's current state
+        (``plan_frontier_dists``): the action of ``act`` together with the
+        distance through each of the six first actions and the set of the
+        shortest."""
+        return env.plan_frontier_dists(mask=mask, out=out)
 
     @torch.no_grad()
     def rollout(self, env: BatchedGridEnv, k_steps: int, obs: Optional[torch.Tensor] = None,

@@ -399,6 +399,40 @@ int vn_copy_agents(VnEnv *dst, const VnEnv *src, const int32_t *src_index, const
 int vn_plan_frontier(VnEnv *env, const uint8_t *mask, int32_t *actions, int32_t *dist, void *stream);
 
 /*
+ * The frontier planner's cost-to-go per action: what vn_plan_frontier knows
+ * and does not return.  With passable, target, the flood R_j and n_k as
+ * defined there, for agent i and action k = 0..5:
+ *   dists[i][k] = j + 1, j the smallest index with n_k in R_j: the number of
+ *                 steps to the nearest target when the first step is action k
+ *               = -1 if n_k is passable but the flood stops growing (or
+ *                 reaches vn_plan_frontier's cap) before it contains n_k
+ *               = -2 if n_k is not passable: outside the room, a known wall,
+ *                 or unknown
+ *   best[i]     a bit set: bit k is set iff dists[i][k] > 0 and equals the
+ *               smallest positive entry; 0 when no entry is positive
+ *   actions[i], dist[i]  exactly what vn_plan_frontier writes, its fallback
+ *               included; when best[i] != 0 they are the lowest set bit of
+ *               best[i] and the smallest positive entry
+ * An agent vn_plan_frontier answers with (0, -1) before it plans (room index
+ * out of range, room larger than the padded size, cell outside its room) gets
+ * dists all -2 and best 0.  Two positive entries differ by at most 2 whenever
+ * the agent's own cell is passable (one step back and on through the other
+ * neighbour), which it is in every state an env reaches by itself.
+ *
+ *   mask     device u8 [N] or NULL = all; rows of unmasked agents are left
+ *            untouched in all four outputs
+ *   actions  device i32 [N], may be NULL
+ *   dist     device i32 [N], may be NULL
+ *   dists    device i32 [N][6]
+ *   best     device u8 [N], may be NULL
+ * One launch, stream-ordered, no host synchronisation; nothing of the env is
+ * written.  VN_ERR_INVALID, with nothing launched: the cases of
+ * vn_plan_frontier (actions may be NULL here), and a NULL dists.
+ */
+int vn_plan_frontier_dists(VnEnv *env, const uint8_t *mask, int32_t *actions, int32_t *dist, int32_t *dists,
+                           uint8_t *best, void *stream);
+
+/*
  * Episode records (both variants): what the reference reports at every
  * episode end -- "Goal Reached! Explored X % after N Steps" / "Truncated
  * after N Steps, with B Bumps and X % of cells discovered"
@@ -850,6 +884,28 @@ int vn_bc_loss(const float *hp, const float *hv, int64_t ldh, const float *wa, c
                const float *bv, const int64_t *src, const int32_t *labels, const uint8_t *weight,
                const float *returns, int32_t M, int32_t F, int32_t A, float ent_coef, float vf_coef, float *dhp,
                float *dhv, float *grad_heads, double *stats, float *part, double *spart, void *stream);
+
+/* vn_bc_loss with a set of equally good actions per sample in place of one
+ * label (csrc/voxnav_bc_loss.hip): label_set uint8, indexed by src like the
+ * other buffers; bit j of it says that action j is optimal (best of
+ * vn_plan_frontier_dists).  S_i = label_set_i & (2^A - 1): bits at or above A
+ * are ignored.  A sample is labelled iff S_i != 0 and its weight is nonzero
+ * (a NULL weight counts as nonzero); n is the number of labelled samples.
+ *   ce_i  = logsumexp_j z_ij - logsumexp_{j in S_i} z_ij      ( = -log sum_{j in S_i} p_ij )
+ *   q_ij  = the softmax of z_i restricted to S_i (0 outside S_i)
+ *   loss  = (1/max(n,1)) sum_{i labelled} ce_i + the entropy and value terms of vn_bc_loss
+ *   dz_ij = (w_i / max(n,1)) (p_ij - q_ij) + the entropy term of vn_bc_loss   (w_i = 1 iff labelled)
+ * Everything else -- the value and entropy terms, the outputs, the workspaces
+ * (vn_bc_loss_part_floats), the errors -- is vn_bc_loss'.  stats[4] is the
+ * share of labelled samples whose argmax (lowest index on ties) lies in S_i,
+ * stats[5] = n / M.  A singleton set is vn_bc_loss with that label; the full
+ * set gives ce_i = 0 and p - q = 0.  Three launches with or without weights:
+ * n depends on the sets, so it is always counted (on the device, an exact
+ * integer sum).  Two calls on the same inputs give the same bits. */
+int vn_bc_loss_set(const float *hp, const float *hv, int64_t ldh, const float *wa, const float *ba, const float *wv,
+                   const float *bv, const int64_t *src, const uint8_t *label_set, const uint8_t *weight,
+                   const float *returns, int32_t M, int32_t F, int32_t A, float ent_coef, float vf_coef, float *dhp,
+                   float *dhv, float *grad_heads, double *stats, float *part, double *spart, void *stream);
 
 /* DAgger's executed action for one collector step (csrc/voxnav_bc_loss.hip):
  * per agent i of N, with the planner's proposal expert[i] / dist[i]

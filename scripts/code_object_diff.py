@@ -14,7 +14,14 @@ agree with addresses dropped and the literal of the PC-relative add after
 ``s_getpc_b64`` masked (that literal, the distance to the unit's constant
 tables or to a callee, shifts with any size change elsewhere in the unit).
 
-  python scripts/code_object_diff.py old/libvoxnav.so new/libvoxnav.so
+A unit that gained or lost kernels has no unit with the same kernel set; it is
+paired with the new unit that shares the most kernel names and gets the same
+per-function report (``paired: "by overlap"``).  ``--rename OLD=NEW`` (any
+number) rewrites function names of the old build before names are compared,
+for a kernel whose mangled name changed and whose code should not have (a
+template that gained a defaulted-false parameter: ``EEEvNS_6BcArgsE=ELb0EEEvNS_6BcArgsE``).
+
+  python scripts/code_object_diff.py old/libvoxnav.so new/libvoxnav.so [--rename OLD=NEW ...]
 """
 from __future__ import annotations
 
@@ -82,8 +89,15 @@ def functions(elf: bytes):
     return {k: (size[k], v) for k, v in out.items()}
 
 
-def function_report(old: bytes, new: bytes):
+def renamed(name: str, renames) -> str:
+    for old, new in renames:
+        name = name.replace(old, new)
+    return name
+
+
+def function_report(old: bytes, new: bytes, renames=()):
     a, b = functions(old), functions(new)
+    a = {renamed(k, renames): v for k, v in a.items()}
     rep = {"identical": sorted(k for k in a if a[k] == b.get(k)), "changed": {}, "only_old": sorted(set(a) - set(b)),
            "only_new": sorted(set(b) - set(a))}
     for k in sorted(set(a) & set(b)):
@@ -92,7 +106,7 @@ def function_report(old: bytes, new: bytes):
     return rep
 
 
-def main(old: Path, new: Path) -> int:
+def main(old: Path, new: Path, renames=()) -> int:
     a, b = units(old), units(new)
     ka = {k for u in a for k in u["kernels"]}
     kb = {k for u in b for k in u["kernels"]}
@@ -104,8 +118,15 @@ def main(old: Path, new: Path) -> int:
         same = v is not None and v["text_sha256"] == u["text_sha256"] and v["objects"] == u["objects"]
         ok = ok and (same or not u["kernels"])
         rep["units"].append({"kernels": len(u["kernels"]), "text_bytes": u["text_bytes"], "identical": same})
+        if v is None and u["kernels"]:
+            names = {renamed(k, renames) for k in u["kernels"]}
+            v = max(b, key=lambda w: len(names & w["kernels"]))
+            if not names & v["kernels"]:
+                continue
+            rep["units"][-1]["paired"] = "by overlap"
         if v is not None and v["text_sha256"] != u["text_sha256"]:
-            rep["units"][-1].update(text_bytes_new=v["text_bytes"], functions=function_report(u["elf"], v["elf"]))
+            rep["units"][-1].update(text_bytes_new=v["text_bytes"],
+                                    functions=function_report(u["elf"], v["elf"], renames))
     rep["kernel_free_units_new"] = [{"text_bytes": u["text_bytes"], "objects": u["objects"]}
                                     for u in b if not u["kernels"]]
     rep["ok"] = ok
@@ -114,4 +135,5 @@ def main(old: Path, new: Path) -> int:
 
 
 if __name__ == "__main__":
-    sys.exit(main(Path(sys.argv[1]), Path(sys.argv[2])))
+    pairs = [tuple(sys.argv[k + 1].split("=", 1)) for k, w in enumerate(sys.argv) if w == "--rename"]
+    sys.exit(main(Path(sys.argv[1]), Path(sys.argv[2]), pairs))

@@ -6,7 +6,8 @@ the same policy untrained, and the frontier planner that taught it (the row of D
 The policy is the reference's (``--policy lstm``: RecurrentActorCriticPolicy, LSTM 256, pi / vf
 [256, 256, 128]; ``mlp``: ActorCriticPolicy with the same MLP).  beta falls linearly from 1 by
 --beta-step per iteration down to --beta-min.  --episodes agents per evaluation, agent i reset with
-seed + i, one deterministic episode each, L 10.  Prints the per-iteration rows, the table and one
+seed + i, one deterministic episode each, L 10.  --labels set trains on the planner's set of equally
+short actions (vn_plan_frontier_dists, vn_bc_loss_set) instead of its lowest-k action.  Prints the per-iteration rows, the table and one
 JSON line.  Needs a GPU."""
 import argparse
 import json
@@ -43,6 +44,8 @@ def main():
     ap.add_argument("--episodes", type=int, default=10)
     ap.add_argument("--L", type=int, default=10)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--labels", choices=["action", "set"], default="action",
+                    help="set: the planner's set of equally short actions as the label (DESIGN.md 10.5)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("warm_start_eval.py needs a GPU")
@@ -55,9 +58,9 @@ def main():
 
     env = BatchedGridEnv(num_agents=args.agents, rooms=load_archive_set(args.train_set), local_map_length=args.L,
                          device=dev)
-    col = DaggerCollector(env, pol, n_steps=args.n_steps)
+    col = DaggerCollector(env, pol, n_steps=args.n_steps, labels=args.labels)
     ln = BCLearner(pol, learning_rate=args.lr, n_epochs=args.epochs, batch_size=args.batch, vf_coef=args.vf_coef,
-                   seed=args.seed)
+                   seed=args.seed, labels=args.labels)
     t0 = time.time()
 
     def show(it, done, st):
@@ -70,7 +73,7 @@ def main():
     torch.cuda.synchronize()
     train_s = time.time() - t0
     env.close()
-    rows["warm-started policy"] = evaluate_policy(pol, eval_rooms, **kw)
+    rows["warm-started policy" + (" (set labels)" if args.labels == "set" else "")] = evaluate_policy(pol, eval_rooms, **kw)
     rows["frontier planner"] = evaluate_planner(eval_rooms, **kw)
     print(f"warm start: {len(hist)} iterations, {hist[-1]['num_timesteps']} env steps, {train_s:.1f} s "
           f"(fused loss minibatches: {ln.fused_updates} of {ln.n_updates})")
