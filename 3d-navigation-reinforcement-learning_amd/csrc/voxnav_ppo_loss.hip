@@ -430,6 +430,11 @@ __global__ __launch_bounds__(256) void grad_norm_kernel(const double *__restrict
 //   g = grad / s;  m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g g
 //   p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)
 // The gradients are read, not rewritten (the learner drops them after the step).
+// A gated step (skip and the step counters both given) counts on the device:
+// adam_count_kernel advances the counters first, only when the step is
+// applied, and adam_kernel takes the step number from counter 0 -- when steps
+// were skipped before, the host's number runs ahead of it, and the bias
+// corrections are then formed here from the applied count.
 struct AdamList {
     float *p[kMaxGradTensors];
     const float *g[kMaxGradTensors];
@@ -440,15 +445,31 @@ struct AdamList {
     int count;
 };
 
+__global__ __launch_bounds__(64) void adam_count_kernel(AdamList al, const int32_t *__restrict__ skip) {
+    if (skip[0] != 0) return;
+    const int k = threadIdx.x;
+    if (k < al.count && al.step[k]) al.step[k][0] += 1.0f;
+}
+
 __global__ __launch_bounds__(256) void adam_kernel(AdamList al, const float *__restrict__ scale,
                                                    const int32_t *__restrict__ skip, float lr, float b1, float b2,
-                                                   float eps, float bc1, float bc2_sqrt, float step_value) {
+                                                   float eps, float bc1, float bc2_sqrt, float step_value,
+                                                   int device_count) {
     if (skip && skip[0] != 0) return;   // gradients from a failed launch: leave every tensor as it was
     const bool div = scale != nullptr;
     const float s = scale ? scale[0] : 1.0f;
-    const float step_size = lr / bc1;
     const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x, stride = (int64_t)gridDim.x * 256;
-    if (gid < al.count && al.step[gid]) al.step[gid][0] = step_value;
+    if (device_count) {
+        // counter 0 was advanced by adam_count_kernel and is only read in this launch
+        const float t = al.step[0][0];
+        if (t != step_value) {
+            bc1 = (float)(1.0 - pow((double)b1, (double)t));
+            bc2_sqrt = (float)sqrt(1.0 - pow((double)b2, (double)t));
+        }
+    } else if (gid < al.count && al.step[gid]) {
+        al.step[gid][0] = step_value;
+    }
+    const float step_size = lr / bc1;
     auto upd = [&](float &pp, float g, float &mm, float &vv) {
         if (div) g = g / s;
         mm = b1 * mm + (1.0f - b1) * g;
@@ -595,8 +616,14 @@ int vn_adam_step(float *const *params, const float *const *grads, float *const *
     const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
     int blocks = (int)((total / 4 + 255) / 256);
     blocks = blocks < 1 ? 1 : (blocks > 2048 ? 2048 : blocks);
+    // gated with counters: the step number is the device's (every counter given, as the launch reads counter 0)
+    int device_count = skip && steps ? 1 : 0;
+    for (int k = 0; device_count && k < count; ++k)
+        if (!al.step[k]) device_count = 0;
+    if (device_count)
+        hipLaunchKernelGGL(adam_count_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, al, skip);
     hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, al, clip_scale, skip, lr, beta1,
-                       beta2, eps, (float)bc1, (float)sqrt(bc2), (float)step);
+                       beta2, eps, (float)bc1, (float)sqrt(bc2), (float)step, device_count);
     VN_HIP(hipGetLastError());
     return VN_OK;
 }

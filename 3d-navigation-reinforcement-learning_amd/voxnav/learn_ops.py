@@ -58,6 +58,10 @@ def mm_tn(a: torch.Tensor, b: torch.Tensor, y: Optional[torch.Tensor] = None, co
     dev = a.device
     if a.stride(2) != 1 or a.stride(1) != M or b.stride(2) != 1 or b.stride(1) != N:
         raise ValueError("mm_tn: operands must be row-contiguous [batch, K, cols]")
+    if y is not None and (y.shape != a.shape or y.stride() != a.stride() or y.dtype != a.dtype or
+                          y.device != a.device):
+        raise ValueError("mm_tn: y must have a's shape, strides, dtype and device (the kernel reads both "
+                         "with one row and batch stride)")
     tiles = -(-M // 128) * -(-N // 128) * Bt
     sp = _splits(K, tiles)
     out = torch.empty((Bt, M, N), dtype=torch.float32, device=dev) if out is None else out
@@ -346,6 +350,9 @@ def grad_norm_scale(params, max_norm: float, work: Optional[torch.Tensor] = None
     if not grads:
         raise ValueError("grad_norm_scale: no gradients")
     dev = grads[0].device
+    grads = [g for g in grads if g.numel()]      # an empty tensor has no address to pass and adds nothing
+    if not grads:
+        return torch.zeros((), dtype=torch.float32, device=dev), torch.ones((), dtype=torch.float32, device=dev)
     for g in grads:
         if g.dtype != torch.float32 or not g.is_contiguous() or g.device != dev:
             raise ValueError("grad_norm_scale: gradients must be contiguous f32 on one device")
@@ -369,7 +376,10 @@ def adam_step(optimizer: torch.optim.Adam, clip_scale: Optional[torch.Tensor] = 
     (``exp_avg``, ``exp_avg_sq``, ``step``), so ``state_dict()`` / checkpoints
     are torch's.  ``skip``: a device int32 word; when it is nonzero at run
     time the step changes nothing (the row-layout LSTM's error word: the
-    gradients of a timed-out launch are never applied)."""
+    gradients of a timed-out launch are never applied) -- parameters, moments
+    and ``step`` stay as they were, and the next applied step is numbered from
+    the device counters (the host's count below may run ahead of them after a
+    skipped step; the kernel then forms the bias corrections itself)."""
     lib = _native.load()
     if len(optimizer.param_groups) != 1:
         raise ValueError("adam_step: one parameter group")
@@ -395,7 +405,9 @@ def adam_step(optimizer: torch.optim.Adam, clip_scale: Optional[torch.Tensor] = 
         for t in (p, p.grad, st["exp_avg"], st["exp_avg_sq"]):
             if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
                 raise ValueError("adam_step: contiguous f32 parameters, gradients and moments on one device")
-    # the step count, kept on the host (read back once after a fresh state or a load_state_dict)
+    # the step count, kept on the host (read back once after a fresh state or a
+    # load_state_dict); for a gated step it is the count of attempts: the
+    # launch checks it against the device counters, which count applied steps
     cache = getattr(optimizer, "_vn_adam_t", None)
     if cache is None or cache[0] is not steps[0]:
         t = int(round(float(steps[0].item())))

@@ -819,6 +819,14 @@ int vn_lstm_rows_bwd(const float *dh_out, const float *w_hh, const float *act, c
  *   vn_gemm_f32_tn      C [M][N] = dZ^T B, dZ [K][M] (as above), B [K][N], K split in
  *                       `splits` (workspace: splits*batch*M*N floats), colsum [batch][M]
  *                       = sum_k dZ[k][m] (workspace2: splits*batch*M), accumulate: C +=
+ *                       (and colsum +=); C is contiguous [batch][M][N] (sc = M N)
+ * Leading dimensions may exceed the row (padding is neither read nor written),
+ * batch strides may be 0 or negative, and no pointer needs more than 4-B
+ * alignment (aligned operands with K % 16 == 0 take the direct-load kernel; the
+ * result does not depend on which kernel runs beyond the summation order).
+ * VN_ERR_INVALID, with nothing launched: a NULL operand, output or workspace;
+ * M, N, K, batch or splits < 1; act = 1 without bias; colsum without
+ * workspace2; sc != M N.
  */
 int vn_gemm_f32_linear(const float *a, int64_t lda, int64_t sa, const float *w, int64_t ldw, int64_t sw,
                        const float *bias, int64_t sbias, float *c, int64_t ldc, int64_t sc, int32_t M, int32_t N,
@@ -842,7 +850,16 @@ int vn_gemm_f32_tn(const float *dy, const float *y, int64_t ldd, int64_t sd, con
  *      d action_net.weight, d action_net.bias, d value_net.weight, d value_net.bias;
  *      stats [6] f64: policy loss, value loss, entropy loss, loss, approx kl,
  *      clip fraction.  adv_sums [128] f64 scratch; part / spart: workspaces of
- *      the sizes vn_ppo_loss_part_floats returns (floats / doubles). */
+ *      the sizes vn_ppo_loss_part_floats returns (floats / doubles).
+ * normalize_advantage: A = (adv - mean) / (std + 1e-8) over the minibatch, std
+ * unbiased.  Equal advantages give A = 0.  With M = 1 the unbiased std of one
+ * sample is NaN, as torch's: the policy loss, the loss, dhp and the action
+ * head's gradients are NaN; the value loss, entropy loss, approx kl, clip
+ * fraction, dhv and the value head's gradients do not depend on A and are
+ * those of the formula.
+ * VN_ERR_INVALID, with nothing launched: a NULL pointer other than src; M < 1;
+ * A outside 1..8; F outside 64..256 or no multiple of 64; ldh < F.
+ * vn_ppo_loss_part_floats: M, F or A < 1. */
 int vn_ppo_loss_part_floats(int32_t M, int32_t F, int32_t A, int64_t *n_part, int64_t *n_spart);
 int vn_ppo_loss(const float *hp, const float *hv, int64_t ldh, const float *wa, const float *ba, const float *wv,
                 const float *bv, const int64_t *src, const int32_t *actions, const float *advantages,
@@ -940,7 +957,13 @@ int vn_grad_norm(const float *const *grads, const int64_t *sizes, int32_t count,
  * state["step"] scalars).  The gradients are not rewritten.  skip (nullable
  * device int32): when *skip != 0 at run time the launch changes nothing --
  * the learner passes the row-layout LSTM's error word (vn_lstm_rows_fwd/bwd
- * `err`), so gradients from a timed-out launch never reach the parameters. */
+ * `err`), so gradients from a timed-out launch never reach the parameters.
+ * With skip and every counter of `steps` given, the counters are the step
+ * count: an applied step advances each by 1 on the device (a skipped one
+ * leaves them), and its bias corrections are those of *steps[0] + 1; `step`
+ * is the caller's expectation of that number, and a caller that does not
+ * read *skip back may pass one that runs ahead after skipped steps.  Two
+ * launches then, one otherwise. */
 int vn_adam_step(float *const *params, const float *const *grads, float *const *exp_avg, float *const *exp_avg_sq,
                  float *const *steps, const int64_t *sizes, int32_t count, const float *clip_scale,
                  const int32_t *skip, float lr,

@@ -8,6 +8,8 @@ different order."""
 import pytest
 import torch
 
+from ppo_loss_helpers import _ppo_loss_reference
+
 pytestmark = pytest.mark.gpu
 
 
@@ -202,31 +204,6 @@ def _dual_lstm_rows_vs_float64(L, B, N, p_start):
         _close(g, p.grad, rel=1e-4)
 
 
-def _ppo_loss_reference(h, wa, ba, wv, bv, act, adv, olp, ret, clip, ent_coef, vf_coef, norm):
-    """sb3's heads + losses in float64 with autograd (RecurrentPPO.train /
-    PPO.train, the block after evaluate_actions)."""
-    h = h.detach().double().requires_grad_(True)
-    P = [t.detach().double().requires_grad_(True) for t in (wa, ba, wv, bv)]
-    logits = h[0] @ P[0].T + P[1]
-    values = (h[1] @ P[2].T + P[3]).flatten()
-    lp_all = torch.log_softmax(logits, -1)
-    lp = lp_all.gather(1, act.long().view(-1, 1)).flatten()
-    ent = -(lp_all.exp() * lp_all).sum(-1)
-    adv = adv.double()
-    if norm:
-        adv = (adv - adv.mean()) / (adv.std() + 1e-8)
-    ratio = torch.exp(lp - olp.double())
-    pl = -torch.min(adv * ratio, adv * torch.clamp(ratio, 1 - clip, 1 + clip)).mean()
-    vl = torch.nn.functional.mse_loss(ret.double(), values)
-    el = -ent.mean()
-    loss = pl + ent_coef * el + vf_coef * vl
-    loss.backward()
-    lr = lp - olp.double()
-    stats = torch.stack([pl, vl, el, loss, ((torch.exp(lr) - 1) - lr).mean(),
-                         ((ratio - 1).abs() > clip).double().mean()]).detach()
-    return h.grad, [p.grad for p in P], stats
-
-
 @pytest.mark.parametrize("M,F,A,gather,norm", [(65536, 128, 6, True, True), (77, 64, 3, False, True),
                                                (4099, 256, 8, True, False), (1, 128, 6, False, False)])
 def test_ppo_loss_matches_float64(M, F, A, gather, norm):
@@ -337,3 +314,209 @@ def test_minibatch_rows_matches_index_arithmetic():
     ref = (idx - env * T) * N + env
     assert torch.equal(src, ref)
     assert torch.equal(rows, obs.reshape(T * N, D)[ref])
+
+
+# vn_adam_step takes its hyperparameters as f32 (include/voxnav.h), so the
+# kernel's Adam is the one with the f32-rounded betas: 1 - beta2 is then
+# 1 - f32(0.999) = 0.99998713e-3, 1.29e-5 (relative) below torch's 1 - 0.999,
+# and with it every second moment -- more than the 1e-5 these tests allow,
+# and not a rounding error of the kernel.  The torch optimizers compared
+# against below are therefore built with the betas the kernel receives.
+# (test_adam_step_matches_torch_fused_adam keeps torch's defaults: at its
+# gradient scale the difference lies below its floor.)
+F32_BETAS = tuple(float(torch.tensor(b, dtype=torch.float32)) for b in (0.9, 0.999))
+
+
+def _adam_pair(shapes, dev, **kw):
+    ps = [torch.nn.Parameter(torch.randn(s, device=dev)) for s in shapes]
+    rs = [torch.nn.Parameter(p.detach().clone()) for p in ps]
+    kw = dict(lr=3e-4, eps=1e-5, betas=F32_BETAS, **kw)
+    return ps, rs, torch.optim.Adam(ps, **kw), torch.optim.Adam(rs, **kw)
+
+
+def _adam_same(opt, ref, ps, rs, step):
+    for p, r in zip(ps, rs):
+        _close(p.detach(), r.detach(), rel=1e-6, floor=1e-7)
+        for k in ("exp_avg", "exp_avg_sq"):
+            _close(opt.state[p][k], ref.state[r][k], rel=1e-5, floor=1e-12)
+        assert float(opt.state[p]["step"]) == float(ref.state[r]["step"]) == step
+
+
+@pytest.mark.parametrize("pattern", [(1, 0, 0), (0, 1, 0, 1, 1, 0), (1, 1, 0)],
+                         ids=lambda p: "".join("SA"[1 - s] for s in p))
+def test_adam_step_skip_gate(pattern):
+    """``adam_step(skip=word)``: with a nonzero word the parameters, both
+    moments and ``state["step"]`` keep their bits; the applied steps before
+    and after equal a torch fused Adam that took only those (bias corrections
+    and ``step`` of the applied count, not of the attempts)."""
+    from voxnav.learn_ops import adam_step, grad_norm_scale
+    dev = "cuda:0"
+    torch.manual_seed(7)
+    ps, rs, opt, ref = _adam_pair([(129, 33), (6, 128), (6,), (333, 7), (1,)], dev, fused=True)
+    word = torch.zeros(1, dtype=torch.int32, device=dev)
+    applied = 0
+    for skipped in pattern:
+        for p, r in zip(ps, rs):
+            g = torch.randn_like(p) * 0.3
+            p.grad, r.grad = g.clone(), g.clone()
+        _, scale = grad_norm_scale(ps, 0.5)
+        word.fill_(3 if skipped else 0)
+        before = [(p.detach().clone(), {k: v.clone() for k, v in opt.state[p].items()}) for p in ps]
+        adam_step(opt, scale, skip=word)
+        if skipped:
+            for p, (p0, st0) in zip(ps, before):
+                assert torch.equal(p.detach().view(torch.int32), p0.view(torch.int32))
+                st = opt.state[p]
+                assert float(st["step"]) == applied
+                assert not st["exp_avg"].any() if not st0 else torch.equal(st["exp_avg"], st0["exp_avg"])
+                assert not st["exp_avg_sq"].any() if not st0 else torch.equal(st["exp_avg_sq"], st0["exp_avg_sq"])
+            continue
+        applied += 1
+        ref.grad_scale = scale.clone()
+        ref.step()
+        ref.grad_scale = None
+        _adam_same(opt, ref, ps, rs, applied)
+    assert applied == pattern.count(0)
+
+
+def test_adam_step_gated_never_skipped_keeps_the_ungated_bits():
+    """A gated step whose word stays 0 and an ungated step give the same bits
+    (parameters, moments, step) over three steps."""
+    from voxnav.learn_ops import adam_step
+    dev = "cuda:0"
+    torch.manual_seed(8)
+    ps, rs, opt, ref = _adam_pair([(129, 33), (6,), (1,)], dev, fused=True)
+    word = torch.zeros(1, dtype=torch.int32, device=dev)
+    for it in range(3):
+        for p, r in zip(ps, rs):
+            g = torch.randn_like(p) * 0.3
+            p.grad, r.grad = g.clone(), g.clone()
+        adam_step(opt, None, skip=word)
+        adam_step(ref, None)
+        for p, r in zip(ps, rs):
+            assert torch.equal(p.detach(), r.detach())
+            for k in ("exp_avg", "exp_avg_sq", "step"):
+                assert torch.equal(opt.state[p][k], ref.state[r][k])
+            assert float(opt.state[p]["step"]) == it + 1
+
+
+def test_adam_step_unaligned_tensors_take_the_scalar_path():
+    """A parameter, a gradient and a moment that are views one float into
+    their storage (not 16-B aligned: the kernel's scalar path), sizes that are
+    no multiple of 4, against torch's fused Adam on aligned copies."""
+    from voxnav.learn_ops import adam_step, grad_norm_scale
+    dev = "cuda:0"
+    torch.manual_seed(11)
+    n = [1027, 515, 259, 1024]
+    off1 = lambda t: torch.cat([t.new_zeros(1), t.flatten()])[1:]  # noqa: E731
+    ps = [torch.nn.Parameter(off1(torch.randn(n[0], device=dev)))] + \
+         [torch.nn.Parameter(torch.randn(k, device=dev)) for k in n[1:]]
+    rs = [torch.nn.Parameter(p.detach().clone()) for p in ps]
+    opt = torch.optim.Adam(ps, lr=3e-4, eps=1e-5, betas=F32_BETAS, fused=True)
+    ref = torch.optim.Adam(rs, lr=3e-4, eps=1e-5, betas=F32_BETAS, fused=True)
+    opt.state[ps[2]] = {"step": torch.zeros((), dtype=torch.float32, device=dev),
+                        "exp_avg": off1(torch.zeros(n[2], device=dev)),
+                        "exp_avg_sq": torch.zeros(n[2], device=dev)}
+    assert ps[0].data_ptr() % 16 == 4 and opt.state[ps[2]]["exp_avg"].data_ptr() % 16 == 4
+    for it in range(2):
+        for i, (p, r) in enumerate(zip(ps, rs)):
+            g = torch.randn_like(r) * 0.3
+            p.grad, r.grad = (off1(g) if i == 1 else g.clone()), g.clone()
+        assert ps[1].grad.data_ptr() % 16 == 4 and ps[3].grad.data_ptr() % 16 == 0
+        norm, scale = grad_norm_scale(ps, 0.5)
+        _close(norm, torch.linalg.vector_norm(torch.cat([r.grad.double().flatten() for r in rs])).float(), rel=1e-6)
+        adam_step(opt, scale)
+        ref.grad_scale = scale.clone()
+        ref.step()
+        ref.grad_scale = None
+        _adam_same(opt, ref, ps, rs, it + 1)
+
+
+def test_adam_step_after_load_state_dict_with_cpu_step():
+    """A state whose ``step`` is a CPU tensor (torch's default Adam, through a
+    state_dict round trip): the next step continues the loaded count -- set on
+    the host when ungated, moved to the device by a gated step."""
+    import copy
+    from voxnav.learn_ops import adam_step
+    dev = "cuda:0"
+    torch.manual_seed(12)
+    ps, rs, first, ref = _adam_pair([(129, 33), (6,), (1,)], dev)
+
+    def grads():
+        for p, r in zip(ps, rs):
+            g = torch.randn_like(p) * 0.3
+            p.grad, r.grad = g.clone(), g.clone()
+
+    grads()
+    first.step()
+    ref.step()
+    opt = torch.optim.Adam(ps, lr=1.0)
+    opt.load_state_dict(copy.deepcopy(first.state_dict()))
+    assert all(opt.state[p]["step"].device.type == "cpu" for p in ps) and opt.param_groups[0]["lr"] == 3e-4
+    grads()
+    adam_step(opt)
+    ref.step()
+    assert all(opt.state[p]["step"].device.type == "cpu" for p in ps)
+    _adam_same(opt, ref, ps, rs, 2)
+    grads()
+    adam_step(opt, skip=torch.zeros(1, dtype=torch.int32, device=dev))
+    ref.step()
+    assert all(opt.state[p]["step"].is_cuda for p in ps)
+    _adam_same(opt, ref, ps, rs, 3)
+
+
+def test_grad_norm_scale_edges():
+    """All-zero gradients (norm 0, divisor 1), exactly 64 tensors, 65 refused,
+    a zero-sized tensor in the list."""
+    from voxnav import _native
+    from voxnav.learn_ops import grad_norm_scale
+    dev = "cuda:0"
+    torch.manual_seed(13)
+
+    def params(sizes, zero=False):
+        ps = [torch.nn.Parameter(torch.zeros(s, device=dev)) for s in sizes]
+        for p in ps:
+            p.grad = torch.zeros_like(p) if zero else torch.randn_like(p) * 0.05
+        return ps
+
+    def ref_norm(ps):
+        return torch.linalg.vector_norm(torch.cat([p.grad.double().flatten() for p in ps])).float()
+
+    norm, scale = grad_norm_scale(params([(33, 7), (5,), (1,)], zero=True), 0.5)
+    assert float(norm) == 0.0 and float(scale) == 1.0
+    ps = params([(i % 7 + 1, i % 5 + 1) for i in range(64)])
+    for max_norm in (0.05, 1e3):
+        norm, scale = grad_norm_scale(ps, max_norm)
+        _close(norm, ref_norm(ps), rel=1e-6)
+        assert abs(scale.item() - max(1.0, (ref_norm(ps).item() + 1e-6) / max_norm)) <= 1e-6 * scale.item()
+    with pytest.raises(_native.VoxnavError):
+        grad_norm_scale(ps + params([(3,)]), 0.5)
+    ps = params([(33, 7), (0,), (5,), (0, 4), (1,)])
+    norm, scale = grad_norm_scale(ps, 0.05)
+    _close(norm, ref_norm(ps), rel=1e-6)
+    assert abs(scale.item() - max(1.0, (ref_norm(ps).item() + 1e-6) / 0.05)) <= 1e-6 * scale.item()
+    norm, scale = grad_norm_scale(params([(0,)]), 0.5)
+    assert float(norm) == 0.0 and float(scale) == 1.0
+
+
+def test_mm_tn_refuses_a_y_of_other_shape_or_strides():
+    """``mm_tn`` reads ``y`` with ``a``'s row and batch strides: any other
+    layout is a ValueError before anything is launched."""
+    from voxnav.learn_ops import mm_tn
+    dev = "cuda:0"
+    torch.manual_seed(14)
+    bt, K, M, N = 2, 40, 12, 8
+    a, b = torch.randn((bt, K, M), device=dev), torch.randn((bt, K, N), device=dev)
+    y = 0.9 * torch.tanh(torch.randn((bt, K, M), device=dev))
+    out = torch.full((bt, M, N), -7.0, device=dev)
+    bad = [y[:, :K - 1], y[0], y[:1].expand(bt, K, M), torch.zeros((bt, K, M + 4), device=dev)[:, :, :M],
+           y.transpose(1, 2).contiguous().transpose(1, 2), torch.zeros((bt, 2 * K, M), device=dev)[:, ::2],
+           y.double(), y.cpu()]
+    for yy in bad:
+        with pytest.raises(ValueError):
+            mm_tn(a, b, y=yy, colsum=True, out=out)
+    torch.cuda.synchronize()
+    assert float(out.min()) == -7.0 == float(out.max())
+    got, _ = mm_tn(a, b, y=y, out=out)
+    z = a.double() * (1 - y.double() ** 2)
+    _close(got.double(), z.transpose(1, 2) @ b.double())
