@@ -19,6 +19,8 @@ include/voxnav.h.  Public API:
   branch.fan_out / branch.evaluate_plans   copies of chosen agents in a wider env; the returns of K-step action plans
   planner.FrontierExplorer / planner.evaluate_planner   the frontier-exploration baseline from the agents' belief maps
   imitate.DaggerCollector / imitate.BCLearner / imitate.warm_start   DAgger warm start from the frontier planner
+  normalize.RewardNormalizer   VecNormalize(norm_reward=True) on the rollout buffer, on the device
+  checkpoint.save_reward_norm / load_reward_norm   its running statistics and returns (.npz)
   sharding            multi-GPU agent sharding helpers
 """
 from . import rooms  # noqa: F401

@@ -103,6 +103,9 @@ _SIGS = {
     "vn_episode_totals": (C.c_int, [P, P, P]),
     "vn_episode_clear": (C.c_int, [P, P, P]),
     "vn_gae": (C.c_int, [P, P, P, P, P, C.c_int32, C.c_int32, C.c_double, C.c_double, P, P, P]),
+    "vn_return_moments": (C.c_int, [P, P, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_double, P, P, P]),
+    "vn_reward_normalize": (C.c_int, [P, C.c_int32, C.c_int32, C.c_int32, P, C.c_int32, P, C.c_double, C.c_double,
+                                      C.c_int32, P, P]),
     "vn_lstm_cell": (C.c_int, [P, C.c_int64, P, P, P, P, P, P, P, C.c_int32, C.c_int32, C.c_int32, P]),
     "vn_policy_head": (C.c_int, [P, P, C.c_int32, C.c_int32, P, P, C.c_int32, P, P, C.c_uint64, C.c_uint64,
                                  C.c_int64, C.c_int32, P, P, P, P]),

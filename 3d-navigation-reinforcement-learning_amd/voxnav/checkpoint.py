@@ -262,3 +262,38 @@ def load_env_state(path: Union[str, Path], env) -> None:
             env.restore(EnvSnapshot(int(z["tag"]), torch.from_numpy(z["blob"]), t))
         else:
             raise ValueError(f"{path}: unknown env state form {form!r}")
+
+
+# ------------------------------------------------------------------ reward normaliser
+REWARD_NORM_VERSION = 1
+
+
+def save_reward_norm(path: Union[str, Path], normalizer) -> Path:
+    """Write a ``voxnav.normalize.RewardNormalizer``'s state to ``path`` (.npz): the running
+    (mean, var, count), the per-agent discounted returns and the constants it was built with
+    (SB3 pickles the VecNormalize wrapper beside the model; this is plain arrays)."""
+    path = Path(path)
+    if path.suffix != ".npz":
+        path = path.with_suffix(".npz")
+    path.parent.mkdir(parents=True, exist_ok=True)
+    sd = normalizer.state_dict()
+    np.savez_compressed(path, format_version=np.int64(REWARD_NORM_VERSION), rms=sd["rms"].numpy(),
+                        ret=sd["ret"].numpy(), num_agents=np.int64(sd["num_agents"]),
+                        agent_id_base=np.int64(sd["agent_id_base"]), gamma=np.float64(sd["gamma"]),
+                        clip_reward=np.float64(sd["clip_reward"]), epsilon=np.float64(sd["epsilon"]))
+    return path
+
+
+def load_reward_norm(path: Union[str, Path], normalizer) -> None:
+    """Put the state saved by ``save_reward_norm`` into ``normalizer``; refused unless it holds the
+    same number of agents (the returns are per agent)."""
+    with np.load(path, allow_pickle=False) as z:
+        if "format_version" not in z.files or int(z["format_version"]) != REWARD_NORM_VERSION:
+            got = int(z["format_version"]) if "format_version" in z.files else None
+            raise ValueError(f"{path}: reward-normaliser format version {got!r}, this build reads "
+                             f"{REWARD_NORM_VERSION}")
+        if int(z["num_agents"]) != normalizer.num_agents:
+            raise ValueError(f"{path}: saved for {int(z['num_agents'])} agents, the normaliser has "
+                             f"{normalizer.num_agents}")
+        normalizer.load_state_dict(dict(rms=torch.from_numpy(z["rms"]), ret=torch.from_numpy(z["ret"]),
+                                        num_agents=int(z["num_agents"])))

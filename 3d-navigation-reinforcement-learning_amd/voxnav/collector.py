@@ -58,6 +58,7 @@ import torch
 from . import _native
 from .env import OBS_DIM, BatchedGridEnv
 from .monitor import EpisodeMonitor
+from .normalize import RewardNormalizer
 from .policy import ActorCriticPolicy, RecurrentActorCriticPolicy
 
 
@@ -227,7 +228,8 @@ class RolloutCollector:
 
     def __init__(self, env: BatchedGridEnv, policy, n_steps: int = 128, gamma: float = 0.99, gae_lambda: float = 0.95,
                  sample_seed: int = 42, deterministic: bool = False, store_lstm_states: bool = True,
-                 reset_seed: int = 42, policy_dtype: str = "f32", monitor: bool = True):
+                 reset_seed: int = 42, policy_dtype: str = "f32", monitor: bool = True,
+                 reward_norm: Optional[RewardNormalizer] = None):
         if not isinstance(policy, (ActorCriticPolicy, RecurrentActorCriticPolicy)):
             raise TypeError("policy must be an ActorCriticPolicy or RecurrentActorCriticPolicy")
         if getattr(policy, "obs_dim", OBS_DIM) != env.obs_dim:
@@ -243,6 +245,15 @@ class RolloutCollector:
         self.deterministic = bool(deterministic)
         self.N = env.num_agents
         self.t_global = 0
+        # VecNormalize(norm_reward=True) on the buffer's rewards (voxnav.normalize); None: raw rewards
+        if reward_norm is not None:
+            if reward_norm.num_agents != env.num_agents or reward_norm.agent_id_base != env.agent_id_base \
+                    or reward_norm.device != torch.device(env.device):
+                raise ValueError("reward_norm must be built for this env's agents (num_agents, agent_id_base) and "
+                                 "device")
+            if reward_norm.gamma != float(gamma):
+                raise ValueError(f"reward_norm discounts by {reward_norm.gamma}, the collector by {float(gamma)}")
+        self.reward_norm = reward_norm
         if policy_dtype not in ("f32", "bf16"):
             raise ValueError("policy_dtype must be 'f32' (the reference's) or 'bf16'")
         self.bf16 = policy_dtype == "bf16"
@@ -568,6 +579,7 @@ class RolloutCollector:
         # are brought up to date after T
         csbuf = rec and self.store and (self.fused or not self.bf16)
         hbuf = csbuf and not self.fused
+        norm, seg0 = self.reward_norm, 0      # steps [seg0, t] are not yet normalised
         for t in range(T):
             self._forward(self._obs[t], t, in_rollout=True)
             self._choose_actions(t)
@@ -596,6 +608,9 @@ class RolloutCollector:
                 2 if zs else 0, s()), "vn_collect_post_step")
             self.t_global += 1
             if (t + 1) % self._flush_every == 0 and t + 1 < T:
+                if norm is not None:               # raw rewards -> normalised, then gamma * V in normalised units
+                    norm.normalize_segment(self.rewards, self._starts, seg0, t + 1, stream=s())
+                    seg0 = t + 1
                 self._bootstrap(self._stash_cnt)   # bounded stash: flush, restart at row 0
                 self._stash_cnt.zero_()
         if csbuf:   # the current (masked) state: lstm_c[T] (lstm_h[T]) with the episode-start mask
@@ -603,7 +618,10 @@ class RolloutCollector:
             torch.where(done, self._zero, self._cs[T], out=self.c)      # no rollout-sized temporaries
             if hbuf:
                 torch.where(done, self._zero, self._hs[T], out=self.h)
-        # the truncation bootstrap of the rest of the rollout
+        # the truncation bootstrap of the rest of the rollout, on normalised rewards (SB3's wrapper
+        # order: VecNormalize scales the reward, collect_rollouts then adds gamma * V(terminal_obs))
+        if norm is not None:
+            norm.normalize_segment(self.rewards, self._starts, seg0, T, stream=s())
         self._bootstrap(self._stash_cnt)
         # V(last obs) under the current (masked) critic state
         if self.recurrent:

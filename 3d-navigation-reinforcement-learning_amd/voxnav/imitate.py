@@ -319,7 +319,8 @@ def warm_start(collector: DaggerCollector, learner: BCLearner, total_timesteps: 
     Returns the per-iteration rows: the train dict (``BCLearner.train``),
     ``beta``, ``num_timesteps``, ``expert_share`` (the mean of
     ``took_expert``), the Monitor and exploration keys ``ppo.learn`` reports
-    and the evaluation's ``eval/*`` keys when one ran."""
+    and the evaluation's ``eval/*`` keys when one ran; with a reward
+    normaliser on the collector its ``ret_rms_var`` / ``ret_rms_mean``."""
     if collector.policy is not learner.policy:
         raise ValueError("collector and learner must share the policy module")
     cbs = [] if callback is None else (list(callback) if isinstance(callback, (list, tuple)) else [callback])
@@ -346,6 +347,9 @@ def warm_start(collector: DaggerCollector, learner: BCLearner, total_timesteps: 
             st["ep_len_mean"] = mon.ep_len_mean()
         if mon is not None and getattr(mon, "last_exploration", None):
             st.update(mon.last_exploration)
+        rn = getattr(collector, "reward_norm", None)
+        if rn is not None:                    # the return statistics the rollout's rewards were scaled by
+            st["ret_rms_var"], st["ret_rms_mean"] = rn.var, rn.mean
         st.update(evals)
         history.append(st)
         stop = False

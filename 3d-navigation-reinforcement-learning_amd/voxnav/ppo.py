@@ -476,7 +476,8 @@ def learn(collector, learner: PPOLearner, total_timesteps: int, callback=None) -
     ``ep_finished_rate``, ``ep_bumps_mean``, ``ep_discovered_mean`` and
     ``ep_coverage`` (discovered cells / max_steps as a ratio of the two sums;
     ``EpisodeMonitor._harvest_exploration``) -- and the evaluation's
-    ``eval/*`` keys when one ran."""
+    ``eval/*`` keys when one ran; with a reward normaliser on the collector
+    (``voxnav.normalize``) its running ``ret_rms_var`` / ``ret_rms_mean``."""
     if collector.policy is not learner.policy:
         raise ValueError("collector and learner must share the policy module")
     cbs = [] if callback is None else (list(callback) if isinstance(callback, (list, tuple)) else [callback])
@@ -499,6 +500,9 @@ def learn(collector, learner: PPOLearner, total_timesteps: int, callback=None) -
             st["ep_len_mean"] = mon.ep_len_mean()
         if mon is not None and getattr(mon, "last_exploration", None):
             st.update(mon.last_exploration)   # this rollout's episodes: ep_finished_rate, ep_bumps_mean, ...
+        rn = getattr(collector, "reward_norm", None)
+        if rn is not None:                    # the return statistics the rollout's rewards were scaled by
+            st["ret_rms_var"], st["ret_rms_mean"] = rn.var, rn.mean
         st.update(evals)
         history.append(st)
         stop = False

@@ -479,6 +479,75 @@ int vn_gae(const float *rewards, const float *values, const float *episode_start
            float *returns, void *stream);
 
 /*
+ * Return-based reward normalisation (SB3 VecNormalize(norm_reward=True):
+ * _update_reward / normalize_reward / RunningMeanStd.update_from_moments; the
+ * reference's other trainer wraps its env so, GARL/train/train_single.py:26),
+ * on the rollout buffer's rewards, before any truncation bootstrap.  This
+ * comment is the rule; csrc/ret_rms.h, the kernels (csrc/voxnav_rnorm.hip)
+ * and the float64 restatement of the tests follow it.
+ *
+ * State: mean, var, count f64, initially 0, 1, 1e-4 (RunningMeanStd(epsilon=
+ * 1e-4)); ret[N] f64, initially 0.  Constants: gamma (the collector's),
+ * epsilon (1e-8), clip (10).
+ *
+ * Per rollout step t, in order, r[t,i] the raw f32 reward:
+ *  1. ret[i] = ret[i] * gamma + (double) r[t,i].
+ *  2. The batch moments of ret over all global agents (global id =
+ *     agent_id_base + i).  Chunk c holds the ids 64c .. 64c+63; m is the
+ *     number of agents present in it (only the last chunk can have m < 64).
+ *     Chunk sum: the xor butterfly over 64 lanes, v_j += v_{j xor s} for
+ *     s = 1, 2, 4, ..., 32, absent lanes holding +0.0; mean_c = sum / m;
+ *     M2_c the same butterfly over (ret - mean_c)^2.  The chunk triples
+ *     (n, mean, M2) are merged pairwise up a binary tree over the global
+ *     chunk index: at each level node j = merge(node 2j, node 2j+1), a node
+ *     without a right sibling passes through.  merge(a, b):
+ *         n = n_a + n_b;  d = mean_b - mean_a;
+ *         mean = mean_a + (d * n_b) / n;
+ *         M2 = (M2_a + M2_b) + (((d * d) * n_a) * n_b) / n.
+ *     The root is (n_B, mean_B, M2_B); var_B = M2_B / n_B.
+ *  3. The running statistics take the batch by the same merge, as SB3 writes
+ *     it: a = (count, mean, var * count), b = (n_B, mean_B, var_B * n_B);
+ *     then count = n, mean = mean, var = M2 / n.
+ *  4. r'[t,i] = (float) clamp(r[t,i] / sqrt(var + epsilon), -clip, clip),
+ *     computed in f64 and rounded once, with the var that includes step t;
+ *     written in place.
+ *  5. ret[i] = 0 where step t ended an episode (dones[t,i] != 0).
+ * Without `update` (SB3's training = False) steps 1-3 and 5 are skipped: ret
+ * and the statistics do not change.  Every operation is one IEEE f64
+ * + - * / sqrt in the stated order (the library is built without
+ * contraction), so the result does not depend on how agents are sharded.
+ *
+ * Two calls, so that a cross-rank gather of the chunk triples can sit between
+ * them.  Both are stream-ordered, read nothing back to the host and use no
+ * floating-point atomics.  Arrays are device memory, rewards / dones f32
+ * [T][N]-major with T >= t1; row t of dones is episode_starts[t + 1].
+ *
+ * vn_return_moments: steps [t0, t1) of this shard's N agents: carries ret
+ *   (f64 [N], read and written back) and writes the chunk triples
+ *   partials[t - t0][c][3] (f64, c < ceil(N / 64) the shard's own chunks).
+ *   VN_ERR_INVALID, nothing launched: a NULL pointer, t0 < 0, t1 <= t0,
+ *   N < 1, agent_id_base < 0 or not a multiple of 64 (waves are aligned to
+ *   global chunks).
+ * vn_reward_normalize: steps [t0, t1) of rewards [.][N].  With update != 0:
+ *   per step the tree merge of the C_global triples of partials
+ *   [t1 - t0][C_global][3] (all ranks' chunks in rank order), then the chain
+ *   over the steps that updates rms (f64 [3]: mean, var, count) and gives
+ *   sqrt(var_t + epsilon) per step, then step 4.  partials is consumed: the
+ *   first triple of each row is overwritten (the row's root, then its scale).
+ *   With update == 0 partials may be NULL and one scale from the stored var
+ *   is used.  scale_out: f64 [t1 - t0], the per-step scales, or NULL.
+ *   VN_ERR_INVALID, nothing launched: NULL rewards / rms (or partials with
+ *   update), t0 < 0, t1 <= t0, t1 - t0 > 65535, N < 1, clip <= 0 or not
+ *   finite, epsilon < 0, and with update a C_global below ceil(N / 64) (this
+ *   shard's own chunks) or above 262144.
+ */
+int vn_return_moments(const float *rewards, const float *dones, int32_t t0, int32_t t1, int32_t N,
+                      int64_t agent_id_base, double gamma, double *ret, double *partials, void *stream);
+int vn_reward_normalize(float *rewards, int32_t t0, int32_t t1, int32_t N, double *partials, int32_t C_global,
+                        double *rms, double epsilon, double clip, int32_t update, double *scale_out,
+                        void *stream);
+
+/*
  * Process options: kernel choices of the entry points that take no handle
  * (the row-layout LSTM and the f32 GEMMs), for A/B timing and the tests of
  * the non-default kernels.  Every choice computes the same function.  Read

@@ -22,6 +22,7 @@ import torch  # noqa: E402
 from voxnav.env import BatchedGridEnv  # noqa: E402
 from voxnav.evaluate import RESULTS_HEADER, evaluate_policy, results_table_row  # noqa: E402
 from voxnav.imitate import BCLearner, DaggerCollector, warm_start  # noqa: E402
+from voxnav.normalize import RewardNormalizer  # noqa: E402
 from voxnav.planner import evaluate_planner  # noqa: E402
 from voxnav.policy import ActorCriticPolicy, RecurrentActorCriticPolicy  # noqa: E402
 from voxnav.rooms import load_archive_set  # noqa: E402
@@ -46,6 +47,8 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--labels", choices=["action", "set"], default="action",
                     help="set: the planner's set of equally short actions as the label (DESIGN.md 10.5)")
+    ap.add_argument("--norm-reward", action="store_true",
+                    help="VecNormalize(norm_reward=True) on the rollout's rewards (DESIGN.md 10.6)")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("warm_start_eval.py needs a GPU")
@@ -58,14 +61,15 @@ def main():
 
     env = BatchedGridEnv(num_agents=args.agents, rooms=load_archive_set(args.train_set), local_map_length=args.L,
                          device=dev)
-    col = DaggerCollector(env, pol, n_steps=args.n_steps, labels=args.labels)
+    rnorm = RewardNormalizer(args.agents, 0.99, device=dev) if args.norm_reward else None
+    col = DaggerCollector(env, pol, n_steps=args.n_steps, labels=args.labels, reward_norm=rnorm)
     ln = BCLearner(pol, learning_rate=args.lr, n_epochs=args.epochs, batch_size=args.batch, vf_coef=args.vf_coef,
                    seed=args.seed, labels=args.labels)
     t0 = time.time()
 
     def show(it, done, st):
         keys = ("beta", "expert_share", "labelled", "bc_loss", "accuracy", "value_loss", "grad_norm", "ep_finished_rate",
-                "ep_bumps_mean", "ep_coverage")
+                "ep_bumps_mean", "ep_coverage", "ret_rms_var")
         print(f"iter {it:3d} steps {done:9d} " + " ".join(f"{k}={st[k]:.4g}" for k in keys if k in st), flush=True)
 
     hist = warm_start(col, ln, total_timesteps=args.iterations * args.agents * args.n_steps,
@@ -73,7 +77,8 @@ def main():
     torch.cuda.synchronize()
     train_s = time.time() - t0
     env.close()
-    rows["warm-started policy" + (" (set labels)" if args.labels == "set" else "")] = evaluate_policy(pol, eval_rooms, **kw)
+    rows["warm-started policy" + (" (set labels)" if args.labels == "set" else "")
+         + (" (normalised rewards)" if args.norm_reward else "")] = evaluate_policy(pol, eval_rooms, **kw)
     rows["frontier planner"] = evaluate_planner(eval_rooms, **kw)
     print(f"warm start: {len(hist)} iterations, {hist[-1]['num_timesteps']} env steps, {train_s:.1f} s "
           f"(fused loss minibatches: {ln.fused_updates} of {ln.n_updates})")
