@@ -256,24 +256,14 @@ class BCLearner(PPOLearner):
     def _update_fused_bc(self, buf, h: torch.Tensor, src: torch.Tensor, labels: torch.Tensor,
                          weight: Optional[torch.Tensor]) -> torch.Tensor:
         """``update`` from the MLP latents h [2, M, F] on: the heads, the loss
-        and its gradient in the fused kernel (learn_ops.bc_loss), the latents'
-        gradient backpropagated through the MLP and LSTM kernels, the head
-        gradients assigned; then (all-reduce), clip, Adam."""
+        and its gradient in the fused kernel (learn_ops.bc_loss / bc_loss_set),
+        then ``PPOLearner._step_fused``."""
         pol = self.policy
         fused = learn_ops.bc_loss_set if self.labels == "set" else learn_ops.bc_loss
         dh, grads, stats = fused(h, pol.action_net, pol.value_net, src, labels, weight, buf.returns.reshape(-1),
                                  self.ent_coef, self.vf_coef)
         self.fused_updates += 1
-        self.optimizer.zero_grad(set_to_none=True)
-        h.backward(dh)
-        for prm, g in zip((pol.action_net.weight, pol.action_net.bias, pol.value_net.weight, pol.value_net.bias),
-                          grads):
-            if prm.requires_grad:
-                prm.grad = g
-        if self.group is not None:
-            self._allreduce_grads()
-        gnorm = self._clip_step()
-        return torch.cat([stats, gnorm.detach().double().view(1)])
+        return self._step_fused(h, dh, grads, stats)
 
     def train(self, buf, epoch_orders: Optional[Sequence] = None) -> Dict[str, float]:
         """One ``train()`` over a ``DaggerBuffer`` (n_epochs passes).  Returns

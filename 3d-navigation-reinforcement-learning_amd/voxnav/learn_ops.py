@@ -211,6 +211,43 @@ def ppo_loss_supported(action_net: torch.nn.Linear, value_net: torch.nn.Linear, 
             value_net.bias is not None)
 
 
+def _head_loss(name: str, h: torch.Tensor, action_net: torch.nn.Linear, value_net: torch.nn.Linear,
+               src: Optional[torch.Tensor], buffers, what: str, scalars, adv_words: int = 0):
+    """What ppo_loss, bc_loss and bc_loss_set share (csrc/head_loss.h is their one kernel): the
+    checks, the workspaces, the call of ``vn_<name>`` and the views of the head gradients.
+    ``buffers``: the entry point's gathered buffers as (tensor or None, dtype), in its argument
+    order; ``scalars``: its arguments between the sizes and the outputs; ``adv_words``: f64
+    words of vn_ppo_loss' advantage sums, passed before the partials."""
+    lib = _native.load()
+    _, M, F = h.shape
+    A = action_net.out_features
+    dev = h.device
+    if h.stride(2) != 1 or h.stride(1) != F:
+        raise ValueError(f"{name}: latents must be row-contiguous [2, M, F]")
+    for t, dt in buffers:
+        if t is not None and (t.dtype != dt or not t.is_contiguous() or t.device != dev):
+            raise ValueError(f"{name}: buffers must be contiguous {what} on the latents' device")
+    if src is not None and (src.dtype != torch.int64 or src.numel() != M or not src.is_contiguous()):
+        raise ValueError(f"{name}: src must be [M] contiguous int64")
+    npart, nspart = C.c_int64(), C.c_int64()
+    sizes = "vn_bc_loss_part_floats" if name.startswith("bc_") else "vn_ppo_loss_part_floats"
+    _native.check(getattr(lib, sizes)(M, F, A, C.byref(npart), C.byref(nspart)), sizes)
+    dh = torch.empty((2, M, F), dtype=torch.float32, device=dev)
+    gh = torch.empty(A * F + A + F + 1, dtype=torch.float32, device=dev)
+    dbl = torch.empty(6 + adv_words + nspart.value, dtype=torch.float64, device=dev)
+    part = torch.empty(npart.value, dtype=torch.float32, device=dev)
+    stats = dbl[:6]
+    wa, ba = action_net.weight.detach(), action_net.bias.detach()
+    wv, bv = value_net.weight.detach(), value_net.bias.detach()
+    adv_sums = (_p(dbl[6:6 + adv_words]),) if adv_words else ()
+    _native.check(getattr(lib, "vn_" + name)(_p(h[0]), _p(h[1]), F, _p(wa.contiguous()), _p(ba), _p(wv.contiguous()),
+                                              _p(bv), _p(src), *[_p(t) for t, _ in buffers], M, F, A, *scalars,
+                                              _p(dh[0]), _p(dh[1]), _p(gh), _p(stats), *adv_sums, _p(part),
+                                              _p(dbl[6 + adv_words:]), _stream(dev)), "vn_" + name)
+    grads = (gh[:A * F].view(A, F), gh[A * F:A * F + A], gh[A * F + A:A * F + A + F].view(1, F), gh[-1:])
+    return dh, grads, stats
+
+
 def ppo_loss(h: torch.Tensor, action_net: torch.nn.Linear, value_net: torch.nn.Linear, src: Optional[torch.Tensor],
              actions: torch.Tensor, advantages: torch.Tensor, old_log_prob: torch.Tensor, returns: torch.Tensor,
              clip_range: float, ent_coef: float, vf_coef: float, normalize_advantage: bool):
@@ -225,34 +262,11 @@ def ppo_loss(h: torch.Tensor, action_net: torch.nn.Linear, value_net: torch.nn.L
     d value_net.bias), stats f64 [6]: policy loss, value loss, entropy loss,
     loss, approx kl, clip fraction).  Nothing is differentiated here: the
     caller backpropagates dh from h and assigns the head gradients."""
-    lib = _native.load()
-    _, M, F = h.shape
-    A = action_net.out_features
-    dev = h.device
-    if h.stride(2) != 1 or h.stride(1) != F:
-        raise ValueError("ppo_loss: latents must be row-contiguous [2, M, F]")
-    for t, dt in ((actions, torch.int32), (advantages, torch.float32), (old_log_prob, torch.float32),
-                  (returns, torch.float32)):
-        if t.dtype != dt or not t.is_contiguous() or t.device != dev:
-            raise ValueError("ppo_loss: buffers must be contiguous int32 actions / f32 values on the latents' device")
-    if src is not None and (src.dtype != torch.int64 or src.numel() != M or not src.is_contiguous()):
-        raise ValueError("ppo_loss: src must be [M] contiguous int64")
-    npart, nspart = C.c_int64(), C.c_int64()
-    _native.check(lib.vn_ppo_loss_part_floats(M, F, A, C.byref(npart), C.byref(nspart)), "vn_ppo_loss_part_floats")
-    dh = torch.empty((2, M, F), dtype=torch.float32, device=dev)
-    gh = torch.empty(A * F + A + F + 1, dtype=torch.float32, device=dev)
-    dbl = torch.empty(6 + 128 + nspart.value, dtype=torch.float64, device=dev)
-    part = torch.empty(npart.value, dtype=torch.float32, device=dev)
-    stats = dbl[:6]
-    wa, ba = action_net.weight.detach(), action_net.bias.detach()
-    wv, bv = value_net.weight.detach(), value_net.bias.detach()
-    _native.check(lib.vn_ppo_loss(_p(h[0]), _p(h[1]), F, _p(wa.contiguous()), _p(ba), _p(wv.contiguous()), _p(bv),
-                                  _p(src), _p(actions), _p(advantages), _p(old_log_prob), _p(returns), M, F, A,
-                                  float(clip_range), float(ent_coef), float(vf_coef), int(bool(normalize_advantage)),
-                                  _p(dh[0]), _p(dh[1]), _p(gh), _p(stats), _p(dbl[6:134]), _p(part), _p(dbl[134:]),
-                                  _stream(dev)), "vn_ppo_loss")
-    grads = (gh[:A * F].view(A, F), gh[A * F:A * F + A], gh[A * F + A:A * F + A + F].view(1, F), gh[-1:])
-    return dh, grads, stats
+    return _head_loss("ppo_loss", h, action_net, value_net, src,
+                      ((actions, torch.int32), (advantages, torch.float32), (old_log_prob, torch.float32),
+                       (returns, torch.float32)), "int32 actions / f32 values",
+                      (float(clip_range), float(ent_coef), float(vf_coef), int(bool(normalize_advantage))),
+                      adv_words=128)
 
 
 def bc_loss(h: torch.Tensor, action_net: torch.nn.Linear, value_net: torch.nn.Linear, src: Optional[torch.Tensor],
@@ -271,33 +285,9 @@ def bc_loss(h: torch.Tensor, action_net: torch.nn.Linear, value_net: torch.nn.Li
     d value_net.bias), stats f64 [6]: cross-entropy, value loss, entropy loss,
     loss, accuracy, labelled share).  Nothing is differentiated here: the
     caller backpropagates dh from h and assigns the head gradients."""
-    lib = _native.load()
-    _, M, F = h.shape
-    A = action_net.out_features
-    dev = h.device
-    if h.stride(2) != 1 or h.stride(1) != F:
-        raise ValueError("bc_loss: latents must be row-contiguous [2, M, F]")
-    for t, dt in ((labels, torch.int32), (weight, torch.uint8), (returns, torch.float32)):
-        if t is not None and (t.dtype != dt or not t.is_contiguous() or t.device != dev):
-            raise ValueError("bc_loss: buffers must be contiguous int32 labels / uint8 weights / f32 returns on the "
-                             "latents' device")
-    if src is not None and (src.dtype != torch.int64 or src.numel() != M or not src.is_contiguous()):
-        raise ValueError("bc_loss: src must be [M] contiguous int64")
-    npart, nspart = C.c_int64(), C.c_int64()
-    _native.check(lib.vn_bc_loss_part_floats(M, F, A, C.byref(npart), C.byref(nspart)), "vn_bc_loss_part_floats")
-    dh = torch.empty((2, M, F), dtype=torch.float32, device=dev)
-    gh = torch.empty(A * F + A + F + 1, dtype=torch.float32, device=dev)
-    dbl = torch.empty(6 + nspart.value, dtype=torch.float64, device=dev)
-    part = torch.empty(npart.value, dtype=torch.float32, device=dev)
-    stats = dbl[:6]
-    wa, ba = action_net.weight.detach(), action_net.bias.detach()
-    wv, bv = value_net.weight.detach(), value_net.bias.detach()
-    _native.check(lib.vn_bc_loss(_p(h[0]), _p(h[1]), F, _p(wa.contiguous()), _p(ba), _p(wv.contiguous()), _p(bv),
-                                 _p(src), _p(labels), _p(weight), _p(returns), M, F, A, float(ent_coef),
-                                 float(vf_coef), _p(dh[0]), _p(dh[1]), _p(gh), _p(stats), _p(part), _p(dbl[6:]),
-                                 _stream(dev)), "vn_bc_loss")
-    grads = (gh[:A * F].view(A, F), gh[A * F:A * F + A], gh[A * F + A:A * F + A + F].view(1, F), gh[-1:])
-    return dh, grads, stats
+    return _head_loss("bc_loss", h, action_net, value_net, src,
+                      ((labels, torch.int32), (weight, torch.uint8), (returns, torch.float32)),
+                      "int32 labels / uint8 weights / f32 returns", (float(ent_coef), float(vf_coef)))
 
 
 def bc_loss_set(h: torch.Tensor, action_net: torch.nn.Linear, value_net: torch.nn.Linear, src: Optional[torch.Tensor],
@@ -310,33 +300,9 @@ def bc_loss_set(h: torch.Tensor, action_net: torch.nn.Linear, value_net: torch.n
     p - softmax restricted to the set; a sample with an empty set is
     unlabelled.  Everything else -- arguments, outputs, stats -- as ``bc_loss``
     (accuracy: the argmax lies in the set).  Three launches."""
-    lib = _native.load()
-    _, M, F = h.shape
-    A = action_net.out_features
-    dev = h.device
-    if h.stride(2) != 1 or h.stride(1) != F:
-        raise ValueError("bc_loss_set: latents must be row-contiguous [2, M, F]")
-    for t, dt in ((label_set, torch.uint8), (weight, torch.uint8), (returns, torch.float32)):
-        if t is not None and (t.dtype != dt or not t.is_contiguous() or t.device != dev):
-            raise ValueError("bc_loss_set: buffers must be contiguous uint8 label sets / uint8 weights / f32 returns "
-                             "on the latents' device")
-    if src is not None and (src.dtype != torch.int64 or src.numel() != M or not src.is_contiguous()):
-        raise ValueError("bc_loss_set: src must be [M] contiguous int64")
-    npart, nspart = C.c_int64(), C.c_int64()
-    _native.check(lib.vn_bc_loss_part_floats(M, F, A, C.byref(npart), C.byref(nspart)), "vn_bc_loss_part_floats")
-    dh = torch.empty((2, M, F), dtype=torch.float32, device=dev)
-    gh = torch.empty(A * F + A + F + 1, dtype=torch.float32, device=dev)
-    dbl = torch.empty(6 + nspart.value, dtype=torch.float64, device=dev)
-    part = torch.empty(npart.value, dtype=torch.float32, device=dev)
-    stats = dbl[:6]
-    wa, ba = action_net.weight.detach(), action_net.bias.detach()
-    wv, bv = value_net.weight.detach(), value_net.bias.detach()
-    _native.check(lib.vn_bc_loss_set(_p(h[0]), _p(h[1]), F, _p(wa.contiguous()), _p(ba), _p(wv.contiguous()), _p(bv),
-                                     _p(src), _p(label_set), _p(weight), _p(returns), M, F, A, float(ent_coef),
-                                     float(vf_coef), _p(dh[0]), _p(dh[1]), _p(gh), _p(stats), _p(part), _p(dbl[6:]),
-                                     _stream(dev)), "vn_bc_loss_set")
-    grads = (gh[:A * F].view(A, F), gh[A * F:A * F + A], gh[A * F + A:A * F + A + F].view(1, F), gh[-1:])
-    return dh, grads, stats
+    return _head_loss("bc_loss_set", h, action_net, value_net, src,
+                      ((label_set, torch.uint8), (weight, torch.uint8), (returns, torch.float32)),
+                      "uint8 label sets / uint8 weights / f32 returns", (float(ent_coef), float(vf_coef)))
 
 
 def grad_norm_scale(params, max_norm: float, work: Optional[torch.Tensor] = None):

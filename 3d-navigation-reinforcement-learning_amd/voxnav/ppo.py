@@ -328,14 +328,20 @@ class PPOLearner:
 
     def _update_fused(self, buf, h: torch.Tensor, src: torch.Tensor, norm: bool) -> torch.Tensor:
         """``update`` from the MLP latents h [2, M, F] on: the heads, losses and
-        their gradient in the fused loss kernel (learn_ops.ppo_loss), the
-        latents' gradient backpropagated through the MLP and LSTM kernels,
-        the head gradients assigned; then (all-reduce), clip, Adam."""
+        their gradient in the fused loss kernel (learn_ops.ppo_loss), then
+        ``_step_fused``."""
         pol = self.policy
         dh, grads, stats = learn_ops.ppo_loss(h, pol.action_net, pol.value_net, src, buf.actions.reshape(-1),
                                               buf.advantages.reshape(-1), buf.log_probs.reshape(-1),
                                               buf.returns.reshape(-1), self.clip_range, self.ent_coef, self.vf_coef,
                                               norm)
+        return self._step_fused(h, dh, grads, stats)
+
+    def _step_fused(self, h: torch.Tensor, dh: torch.Tensor, grads, stats: torch.Tensor) -> torch.Tensor:
+        """The rest of an update after a fused head loss (learn_ops.ppo_loss, bc_loss,
+        bc_loss_set): dh backpropagated from h, the head gradients assigned, (all-reduce),
+        clip, Adam.  Returns the loss's stats with the gradient norm appended."""
+        pol = self.policy
         self.optimizer.zero_grad(set_to_none=True)
         h.backward(dh)
         for prm, g in zip((pol.action_net.weight, pol.action_net.bias, pol.value_net.weight, pol.value_net.bias),

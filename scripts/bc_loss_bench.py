@@ -7,8 +7,10 @@ around each call (its two or three launches), median of --reps timed repetitions
 
 The BC kernel does strictly less (no advantage pass without weights, two fewer gathered streams),
 so it should not be slower; the bound is 1.15 x the vn_ppo_loss median of the same run, the
-10-15 % placement noise of DESIGN.md 7.  Prints one JSON line; exit status 1 when a ratio exceeds
-the bound.  Needs a GPU."""
+10-15 % placement noise of DESIGN.md 7.  vn_bc_loss_set (always counted, a second softmax over the
+set) is timed beside them and its ratio reported, not bounded.  --lib PATH runs another build of
+the library (A/B against a parent build).  Prints one JSON line; exit status 1 when a ratio
+exceeds the bound.  Needs a GPU."""
 import argparse
 import json
 import statistics
@@ -19,7 +21,8 @@ REPO = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(REPO / "3d-navigation-reinforcement-learning_amd"))
 import torch  # noqa: E402
 
-from voxnav.learn_ops import bc_loss, ppo_loss  # noqa: E402
+from voxnav import _native  # noqa: E402
+from voxnav.learn_ops import bc_loss, bc_loss_set, ppo_loss  # noqa: E402
 
 BOUND = 1.15
 
@@ -48,7 +51,10 @@ def main():
     ap.add_argument("--widths", type=int, nargs="+", default=[128, 256])
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--lib", type=Path, default=None, help="run this build of libvoxnav.so")
     args = ap.parse_args()
+    if args.lib is not None:
+        _native.use_library(args.lib.resolve())
     if not torch.cuda.is_available():
         raise SystemExit("bc_loss_bench.py needs a GPU")
     dev = torch.device("cuda:0")
@@ -59,7 +65,9 @@ def main():
     act = torch.randint(0, A, (R,), device=dev, dtype=torch.int32)
     adv, olp, ret = torch.randn(R, device=dev), torch.randn(R, device=dev) - 1.8, torch.randn(R, device=dev)
     wgt = (torch.rand(R, device=dev) < 0.9).to(torch.uint8)
-    res = {"M": M, "A": A, "reps": args.reps, "warmup": args.warmup, "bound": BOUND, "widths": {}}
+    sets = ((1 << act) | torch.randint(0, 1 << A, (R,), device=dev)).to(torch.uint8)   # the label and random others
+    res = {"lib": None if args.lib is None else str(args.lib), "M": M, "A": A, "reps": args.reps,
+           "warmup": args.warmup, "bound": BOUND, "widths": {}}
     ok = True
     for F in args.widths:
         an, vn = torch.nn.Linear(F, A).to(dev), torch.nn.Linear(F, 1).to(dev)
@@ -68,11 +76,12 @@ def main():
             "ppo_loss": lambda: ppo_loss(h, an, vn, src, act, adv, olp, ret, 0.2, 0.01, 0.5, True),
             "bc_loss": lambda: bc_loss(h, an, vn, src, act, None, ret, 0.0, 0.5),
             "bc_loss_weights": lambda: bc_loss(h, an, vn, src, act, wgt, ret, 0.0, 0.5),
+            "bc_loss_set": lambda: bc_loss_set(h, an, vn, src, sets, wgt, ret, 0.0, 0.5),
         }
         r = {name: timed(fn, args.reps, args.warmup, dev) for name, fn in cases.items()}
-        for name in ("bc_loss", "bc_loss_weights"):
+        for name in ("bc_loss", "bc_loss_weights", "bc_loss_set"):
             r[name]["ratio_to_ppo_loss"] = round(r[name]["median_ms"] / r["ppo_loss"]["median_ms"], 4)
-            ok = ok and r[name]["ratio_to_ppo_loss"] <= BOUND
+            ok = ok and (name == "bc_loss_set" or r[name]["ratio_to_ppo_loss"] <= BOUND)
         res["widths"][str(F)] = r
     res["within_bound"] = ok
     print(json.dumps(res))

@@ -1,0 +1,85 @@
+#!/usr/bin/env python3
+"""Output bits of the three head losses (csrc/head_loss.h: vn_ppo_loss, vn_bc_loss, vn_bc_loss_set)
+on a fixed seeded list of cases, for comparing two builds of the library: a change that must leave
+the arithmetic alone gives the same file from both.
+
+Cases: all 16 (Q, AM) kernel instantiations at M = 129 (F in 64..256, A in {2, 4, 6, 8}), and
+M in {1, 3, 33, 257} at (F, A) = (192, 5) and (128, 6); every case gathered through src.  Per case:
+ppo_loss raw and with normalised advantages, bc_loss without and with weights, bc_loss_set (with
+weights).  Per call one sha256 of each output's bytes: dh, the four head gradients, stats.
+
+  python scripts/head_loss_bits.py --lib PATH/libvoxnav.so --out bits.json
+
+Needs a GPU; the whole run takes seconds."""
+import argparse
+import hashlib
+import json
+import sys
+from pathlib import Path
+
+REPO = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(REPO / "3d-navigation-reinforcement-learning_amd"))
+import torch  # noqa: E402
+
+from voxnav import _native  # noqa: E402
+from voxnav.learn_ops import bc_loss, bc_loss_set, ppo_loss  # noqa: E402
+
+CASES = [(129, F, A) for F in (64, 128, 192, 256) for A in (2, 4, 6, 8)] + \
+        [(M, F, A) for F, A in ((192, 5), (128, 6)) for M in (1, 3, 33, 257)]
+NAMES = ("dh", "d_action_weight", "d_action_bias", "d_value_weight", "d_value_bias", "stats")
+
+
+def sha(t):
+    return hashlib.sha256(t.detach().contiguous().cpu().numpy().tobytes()).hexdigest()
+
+
+def digests(out):
+    dh, grads, stats = out
+    return dict(zip(NAMES, map(sha, (dh, *grads, stats))))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--lib", type=Path, required=True, help="the build of libvoxnav.so to run")
+    ap.add_argument("--out", type=Path, default=None, help="write the JSON here (default: stdout)")
+    args = ap.parse_args()
+    _native.use_library(args.lib.resolve())
+    if not torch.cuda.is_available():
+        raise SystemExit("head_loss_bits.py needs a GPU")
+    dev = torch.device("cuda:0")
+    res = {}
+    for M, F, A in CASES:
+        # inputs drawn on the CPU: the same bits whatever the device's generator does
+        g = torch.Generator().manual_seed(100000 * M + 10 * F + A)
+        rand = lambda *s: torch.randn(*s, generator=g)  # noqa: E731
+        R = M + 1000
+        an, vn = torch.nn.Linear(F, A), torch.nn.Linear(F, 1)
+        with torch.no_grad():
+            for p in (*an.parameters(), *vn.parameters()):
+                p.copy_(rand(*p.shape) / F ** 0.5)
+        an, vn = an.to(dev), vn.to(dev)
+        h = torch.tanh(rand(2, M, F)).to(dev)
+        src = torch.randperm(R, generator=g)[:M].contiguous().to(dev)
+        act = torch.randint(0, A, (R,), generator=g, dtype=torch.int32).to(dev)
+        adv, olp, ret = rand(R).to(dev), (rand(R) - 1.8).to(dev), rand(R).to(dev)
+        wgt = (torch.rand(R, generator=g) < 0.7).to(torch.uint8).to(dev)
+        sets = torch.randint(0, 256, (R,), generator=g).to(torch.uint8).to(dev)    # empty sets and bits above A too
+        res[f"M={M} F={F} A={A}"] = {
+            "ppo_loss": digests(ppo_loss(h, an, vn, src, act, adv, olp, ret, 0.2, 0.01, 0.5, False)),
+            "ppo_loss_normalised": digests(ppo_loss(h, an, vn, src, act, adv, olp, ret, 0.2, 0.01, 0.5, True)),
+            "bc_loss": digests(bc_loss(h, an, vn, src, act, None, ret, 0.01, 0.5)),
+            "bc_loss_weights": digests(bc_loss(h, an, vn, src, act, wgt, ret, 0.01, 0.5)),
+            "bc_loss_set": digests(bc_loss_set(h, an, vn, src, sets, wgt, ret, 0.01, 0.5)),
+        }
+    text = json.dumps(res, indent=1, sort_keys=True)
+    if args.out is None:
+        print(text)
+    else:
+        args.out.parent.mkdir(parents=True, exist_ok=True)
+        args.out.write_text(text + "\n")
+        print(f"{len(res)} cases -> {args.out}")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -44,20 +44,13 @@ BC_MODES = [(False, None, 0.01, 0.5), (True, "random", 0.0, 0.5), (True, "zero",
             (False, "random", 0.01, 0.0), (True, None, 0.0, 0.5), (False, "zero", 0.0, 0.5)]
 
 
-@pytest.mark.parametrize("A", [1, 6, 8])
-@pytest.mark.parametrize("F", [64, 256])
-@pytest.mark.parametrize("M", BC_M)
-def test_bc_loss_set_matches_float64(M, F, A):
-    """Tolerances of tests/test_imitate_gpu.py::test_bc_loss_matches_float64: latent gradients 2e-5,
-    head gradients 1e-4, logged sums 1e-5 relative; accuracy and labelled share exact.  Two calls
-    on the same inputs give the same bits.  Sets: 30 % empty, 25 % singletons, random bits at or
-    above A."""
+def _bc_loss_set_against_float64(M, F, A, modes):
     from voxnav.learn_ops import bc_loss_set
     torch.manual_seed(1000 * M + F + A)
     rng = np.random.default_rng(1000 * M + F + A)
     an, vn = torch.nn.Linear(F, A).to(DEV), torch.nn.Linear(F, 1).to(DEV)
     h = torch.tanh(torch.randn((2, M, F), device=DEV))
-    for gather, wmode, ent, vf in BC_MODES:
+    for gather, wmode, ent, vf in modes:
         R = M + 1000 if gather else M
         src = torch.randperm(R, device=DEV)[:M].contiguous() if gather else None
         sets = torch.as_tensor(bs.random_sets(rng, (R,), A), device=DEV)
@@ -86,6 +79,30 @@ def test_bc_loss_set_matches_float64(M, F, A):
             assert st[0] == 0.0 and st[4] == 0.0 and st[5] == 0.0
             if ent == 0.0:
                 assert float(dh[0].abs().max()) == 0.0
+
+
+@pytest.mark.parametrize("A", [1, 6, 8])
+@pytest.mark.parametrize("F", [64, 256])
+@pytest.mark.parametrize("M", BC_M)
+def test_bc_loss_set_matches_float64(M, F, A):
+    """Tolerances of tests/test_imitate_gpu.py::test_bc_loss_matches_float64: latent gradients 2e-5,
+    head gradients 1e-4, logged sums 1e-5 relative; accuracy and labelled share exact.  Two calls
+    on the same inputs give the same bits.  Sets: 30 % empty, 25 % singletons, random bits at or
+    above A."""
+    _bc_loss_set_against_float64(M, F, A, BC_MODES)
+
+
+# every instantiation of the loss kernel at one full block plus one sample
+# (tests/test_imitate_gpu.py::test_bc_loss_grid_matches_float64, on label sets)
+GRID_MODES = {"src+weights": (True, "random", 0.01, 0.5), "plain": (False, None, 0.01, 0.5)}
+
+
+@pytest.mark.parametrize("mode", list(GRID_MODES))
+@pytest.mark.parametrize("A", range(1, 9))
+@pytest.mark.parametrize("F", [64, 128, 192, 256])
+def test_bc_loss_set_grid_matches_float64(F, A, mode):
+    """test_bc_loss_set_matches_float64's checks and tolerances on all 32 (F, A) pairs at M = 129."""
+    _bc_loss_set_against_float64(129, F, A, [GRID_MODES[mode]])
 
 
 def test_random_sets_hold_what_the_test_is_for():
