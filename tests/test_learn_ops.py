@@ -204,6 +204,54 @@ def _dual_lstm_rows_vs_float64(L, B, N, p_start):
         _close(g, p.grad, rel=1e-4)
 
 
+@pytest.mark.parametrize("layout", ["auto", "units16", "units32"])
+@pytest.mark.parametrize("L,B,N,p_start", [(9, 37, 40, 0.2), (2, 33, 8, 0.5)])
+def test_dual_lstm_rows_input_gradient_matches_float64(L, B, N, p_start, layout):
+    """The row-layout backward with an input that needs a gradient (dG is
+    only allocated and written then): x.grad and the eight parameter
+    gradients against float64 autograd, and the parameter gradients
+    bit-identical to a run whose x needs none (the learner's own case)."""
+    from types import SimpleNamespace
+    from voxnav import _native, lstm_seq
+    dev = "cuda:0"
+    D, H = 80, 256
+    torch.manual_seed(L * B + N + 1)
+    la, lc = torch.nn.LSTM(D, H).to(dev), torch.nn.LSTM(D, H).to(dev)
+    pol = SimpleNamespace(lstm_actor=la, lstm_critic=lc)
+    if not lstm_seq.rows_supported(pol, D, B):
+        pytest.skip("row-layout kernels not co-resident on this device")
+    x = torch.randn((L, B, D), device=dev)
+    env = torch.randint(0, N, (L, B), device=dev, dtype=torch.int32)
+    start = (torch.rand((L, B), device=dev) < p_start).to(torch.uint8)
+    start[0] = 1
+    keep = (torch.rand((L, B), device=dev) > 0.3).float()
+    hs = 0.5 * torch.randn((L, 2, N, H), device=dev)
+    cs = 0.5 * torch.randn((L, 2, N, H), device=dev)
+    dy = torch.randn((2, L, B, H), device=dev)
+    params = list(la.parameters()) + list(lc.parameters())
+    runs = []
+    with _native.option("rows_layout", {"auto": 0, "units32": 1, "units16": 2}[layout]):
+        for need_dx in (True, False):
+            xin = x.clone().requires_grad_(need_dx)
+            oa, oc = lstm_seq.dual_lstm_rows(pol, xin, env, start, keep, hs, cs)
+            ((oa * dy[0]).sum() + (oc * dy[1]).sum()).backward()
+            runs.append(([p.grad.clone() for p in params], xin.grad))
+            lstm_seq.rows_check(torch.device(dev))
+            for p in params:
+                p.grad = None
+    (got, dx), (got_no_dx, none) = runs
+    assert none is None and dx.shape == x.shape
+    for a, b in zip(got, got_no_dx):
+        assert torch.equal(a, b)
+    x64 = x.double().requires_grad_()
+    ra = _rows_reference(x64, env, start, keep, hs, cs, la, 0)
+    rc = _rows_reference(x64, env, start, keep, hs, cs, lc, 1)
+    ((ra * dy[0].double()).sum() + (rc * dy[1].double()).sum()).backward()
+    _close(dx, x64.grad, rel=1e-4)
+    for g, p in zip(got, params):
+        _close(g, p.grad, rel=1e-4)
+
+
 @pytest.mark.parametrize("M,F,A,gather,norm", [(65536, 128, 6, True, True), (77, 64, 3, False, True),
                                                (4099, 256, 8, True, False), (1, 128, 6, False, False)])
 def test_ppo_loss_matches_float64(M, F, A, gather, norm):
