@@ -1,6 +1,7 @@
 // head_loss.h -- the fused "head loss" of the learner, once: the skeleton that
-// vn_ppo_loss (voxnav_ppo_loss.hip) and vn_bc_loss / vn_bc_loss_set
-// (voxnav_bc_loss.hip) share; their file headers state the formulas.  Common
+// vn_ppo_loss (voxnav_ppo_loss.hip), vn_bc_loss / vn_bc_loss_set
+// (voxnav_bc_loss.hip) and vn_ppo_bc_loss / vn_ppo_bc_loss_set
+// (voxnav_ppo_bc_loss.hip) share; their file headers state the formulas.  Common
 // to them, with lp = log_softmax(z), p = exp(lp), H the entropy:
 //   dz_j = (the objective's policy term)_j + (ent_coef / M) p_j (lp_j + H)
 //   dv   = vf_coef 2 (v - ret) / M
@@ -13,8 +14,9 @@
 // value term, the gradient accumulation and stores, the group / wave / block
 // fold into per-block partials (f32 head gradients, f64 logged sums: slot 1 the
 // squared value error, slot 2 the entropy), and the reduce kernel that sums the
-// partials in a fixed order.  An objective (a plain struct: PpoClip, BcLabel,
-// BcSet in the two units) supplies what differs:
+// partials in a fixed order.  An objective (a plain struct: PpoClip in
+// ppo_objective.h, BcLabel / BcSet in bc_objective.h, PpoBc<> composed of them
+// in voxnav_ppo_bc_loss.hip) supplies what differs:
 //   kStats            f64 sums per block (slots 0, 3.. are the objective's)
 //   begin(M)          block-uniform values, every thread (e.g. 1 / labelled) -> Obj::Block
 //   gather(b, r, A)   the sample's own gathered inputs -> Obj::Sample

@@ -19,6 +19,7 @@ include/voxnav.h.  Public API:
   branch.fan_out / branch.evaluate_plans   copies of chosen agents in a wider env; the returns of K-step action plans
   planner.FrontierExplorer / planner.evaluate_planner   the frontier-exploration baseline from the agents' belief maps
   imitate.DaggerCollector / imitate.BCLearner / imitate.warm_start   DAgger warm start from the frontier planner
+  KickstartLearner / kickstart   PPO with a decaying cross-entropy to the planner's labels (imitate)
   normalize.RewardNormalizer   VecNormalize(norm_reward=True) on the rollout buffer, on the device
   checkpoint.save_reward_norm / load_reward_norm   its running statistics and returns (.npz)
   sharding            multi-GPU agent sharding helpers
@@ -27,7 +28,8 @@ from . import rooms  # noqa: F401
 from ._native import VoxnavError, load as load_library  # noqa: F401
 
 __all__ = ["rooms", "BatchedGridEnv", "VoxnavVecEnv", "GridAgent", "SimpleGridAgent", "RolloutCollector", "compute_gae",
-           "PPOLearner", "evaluate_policy", "save_checkpoint", "load_checkpoint", "VoxnavError", "load_library"]
+           "PPOLearner", "evaluate_policy", "save_checkpoint", "load_checkpoint", "VoxnavError", "load_library",
+           "KickstartLearner", "kickstart"]
 
 
 def __getattr__(name):
@@ -59,4 +61,7 @@ def __getattr__(name):
     if name in ("save_checkpoint", "load_checkpoint"):
         from . import checkpoint
         return getattr(checkpoint, name)
+    if name in ("KickstartLearner", "kickstart"):
+        from . import imitate
+        return getattr(imitate, name)
     raise AttributeError(name)

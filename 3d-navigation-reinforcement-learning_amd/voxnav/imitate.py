@@ -17,6 +17,11 @@ Online Learning", AISTATS 2011):
   autograd elsewhere.  Minibatches, the LSTM re-run from the stored states,
   the all-reduce, the clip and the Adam step are the parent's.
 * ``warm_start``: ``ppo.learn``'s loop over the two, with a beta schedule.
+* ``KickstartLearner`` / ``kickstart``: PPO on the policy's own rollouts
+  (beta = 0) with the cross-entropy to the planner's labels added under a
+  coefficient that the loop lets decay to 0 (Schmitt et al., "Kickstarting
+  Deep Reinforcement Learning", 2018), through the fused
+  kernel ``learn_ops.ppo_bc_loss`` (csrc/voxnav_ppo_bc_loss.hip).
 
 The policy module is the one ``PPOLearner``, ``save_checkpoint`` and
 ``evaluate_policy`` take: a warm start followed by ``ppo.learn`` needs no
@@ -30,12 +35,13 @@ from typing import Callable, Dict, List, Optional, Sequence, Union
 
 import numpy as np
 import torch
+import torch.nn.functional as Fn
 
 from . import _native, learn_ops
 from .collector import RolloutBuffer, RolloutCollector, _p
 from .env import BatchedGridEnv, FrontierDists
 from .planner import FrontierExplorer
-from .ppo import PPOLearner
+from .ppo import PPOLearner, run_loop
 
 PLANNER_MAX_PAD = 64     # vn_plan_frontier's bound on the padded width and depth
 
@@ -82,6 +88,22 @@ def _check_beta(beta) -> float:
     if not 0.0 <= b <= 1.0:
         raise ValueError(f"beta must be in [0, 1], got {beta!r}")
     return b
+
+
+def _buffer_labels(buf, labels: str, who: str):
+    """The flat labels (``expert_set`` or ``expert_actions``) and label weights (or None) of a
+    buffer for learner ``who``; raises where the buffer does not carry them."""
+    if labels == "set":
+        lab = getattr(buf, "expert_set", None)
+        if lab is None:
+            raise ValueError(f"{who}(labels='set') needs the buffer's expert_set (a DaggerCollector with "
+                             "labels='set')")
+    else:
+        lab = getattr(buf, "expert_actions", None)
+        if lab is None:
+            raise ValueError(f"{who} needs the buffer's expert_actions (a DaggerBuffer)")
+    w = getattr(buf, "label_weight", None)
+    return lab.reshape(-1), (None if w is None else w.reshape(-1))
 
 
 class DaggerCollector(RolloutCollector):
@@ -180,17 +202,7 @@ class BCLearner(PPOLearner):
         self.labels = _check_labels(labels)
 
     def _labels(self, buf):
-        if self.labels == "set":
-            lab = getattr(buf, "expert_set", None)
-            if lab is None:
-                raise ValueError("BCLearner(labels='set') needs the buffer's expert_set (a DaggerCollector with "
-                                 "labels='set')")
-        else:
-            lab = getattr(buf, "expert_actions", None)
-            if lab is None:
-                raise ValueError("BCLearner needs the buffer's expert_actions (a DaggerBuffer)")
-        w = getattr(buf, "label_weight", None)
-        return lab.reshape(-1), (None if w is None else w.reshape(-1))
+        return _buffer_labels(buf, self.labels, type(self).__name__)
 
     def update(self, buf, idx: torch.Tensor, packed: Optional[dict] = None) -> torch.Tensor:
         """One minibatch (env-major flat ids ``idx``): loss, backward,
@@ -271,26 +283,8 @@ class BCLearner(PPOLearner):
         labelled samples), ``value_loss``, ``entropy_loss``, ``loss``,
         ``accuracy`` (labelled samples whose argmax is the label), ``labelled``
         (their share), ``grad_norm``, and ``n_minibatches``, ``n_updates``."""
-        T, N = buf.actions.shape
-        total = T * N
-        dev = buf.actions.device
         self._labels(buf)
-        if self.recurrent and (buf.lstm_h is None or buf.lstm_c is None):
-            raise ValueError("the recurrent learner needs the buffer's LSTM states (store_lstm_states=True)")
-        orders = list(epoch_orders) if epoch_orders is not None else self._orders(total)
-        acc = torch.zeros(7, dtype=torch.float64, device=dev)
-        n_mb = 0
-        self.policy.train()
-        for order in orders:
-            if self.recurrent:
-                perm = torch.roll(torch.arange(total, device=dev), -int(order))
-            else:
-                perm = torch.as_tensor(np.asarray(order), dtype=torch.int64, device=dev)
-            logs = self.update_many(buf, [perm[s:s + self.batch_size] for s in range(0, total, self.batch_size)],
-                                    windows=self.recurrent)
-            acc += logs.sum(0)
-            n_mb += logs.shape[0]
-        m = (acc / max(1, n_mb)).tolist()
+        m, n_mb = self._run_epochs(buf, epoch_orders)
         return dict(bc_loss=m[0], value_loss=m[1], entropy_loss=m[2], loss=m[3], accuracy=m[4], labelled=m[5],
                     grad_norm=m[6], n_minibatches=n_mb, n_updates=self.n_updates)
 
@@ -311,41 +305,163 @@ def warm_start(collector: DaggerCollector, learner: BCLearner, total_timesteps: 
     ``took_expert``), the Monitor and exploration keys ``ppo.learn`` reports
     and the evaluation's ``eval/*`` keys when one ran; with a reward
     normaliser on the collector its ``ret_rms_var`` / ``ret_rms_mean``."""
-    if collector.policy is not learner.policy:
-        raise ValueError("collector and learner must share the policy module")
-    cbs = [] if callback is None else (list(callback) if isinstance(callback, (list, tuple)) else [callback])
-    per_rollout = collector.n_steps * collector.N
-    done, it, history = 0, 0, []
-    while done < total_timesteps:
+    def begin(it):
         b = float(beta(it)) if callable(beta) else float(beta)
         collector.set_beta(b)
-        buf = collector.collect()
-        done += per_rollout
-        it += 1
-        evals = {}
-        for cb in cbs:
-            if hasattr(cb, "on_rollout_end"):
-                evals.update(cb.on_rollout_end(learner.policy, done, collector.n_steps, learner.optimizer) or {})
-        st = learner.train(buf)
-        collector.sync_weights()
-        st["beta"] = b
-        st["num_timesteps"] = done
-        st["expert_share"] = float(buf.took_expert.float().mean())
-        mon = getattr(collector, "monitor", None)
-        if mon is not None and mon.ep_info_buffer:
-            st["ep_rew_mean"] = mon.ep_rew_mean()
-            st["ep_len_mean"] = mon.ep_len_mean()
-        if mon is not None and getattr(mon, "last_exploration", None):
-            st.update(mon.last_exploration)
-        rn = getattr(collector, "reward_norm", None)
-        if rn is not None:                    # the return statistics the rollout's rewards were scaled by
-            st["ret_rms_var"], st["ret_rms_mean"] = rn.var, rn.mean
-        st.update(evals)
-        history.append(st)
-        stop = False
-        for cb in cbs:
-            if not hasattr(cb, "on_rollout_end") and callable(cb) and cb(it, done, st) is False:
-                stop = True
-        if stop:
-            break
-    return history
+        return {"beta": b}
+
+    return run_loop(collector, learner, total_timesteps, callback, begin=begin,
+                    extra=lambda buf: {"expert_share": float(buf.took_expert.float().mean())})
+
+
+def _check_bc_coef(c) -> float:
+    v = float(c)
+    if not (np.isfinite(v) and v >= 0.0):
+        raise ValueError(f"bc_coef must be finite and >= 0, got {c!r}")
+    return v
+
+
+class KickstartLearner(PPOLearner):
+    """PPO with an auxiliary cross-entropy to the planner's labels on the
+    policy's own rollouts (kickstarting): per minibatch
+        loss = PPO's loss + bc_coef * CE(labelled samples)
+    (the formula of include/voxnav.h vn_ppo_bc_loss), with the parent's
+    minibatch order, LSTM re-run, all-reduce, grad-norm clip and Adam step.
+    ``train()`` takes a ``DaggerBuffer`` collected with beta = 0: with an
+    executed planner action the importance ratio would pair an action with
+    another action's old log-prob (``DaggerBuffer``).  ``labels`` as
+    ``BCLearner``'s.  With a process group the ranks' gradients are averaged
+    equally, although their labelled counts may differ."""
+
+    def __init__(self, policy, learning_rate: float = 3e-4, n_epochs: int = 10, batch_size: int = 64,
+                 clip_range: float = 0.2, ent_coef: float = 0.01, vf_coef: float = 0.5, max_grad_norm: float = 0.5,
+                 normalize_advantage: bool = True, seed: int = 0, process_group=None, bc_coef: float = 1.0,
+                 labels: str = "action"):
+        super().__init__(policy, learning_rate=learning_rate, n_epochs=n_epochs, batch_size=batch_size,
+                         clip_range=clip_range, ent_coef=ent_coef, vf_coef=vf_coef, max_grad_norm=max_grad_norm,
+                         normalize_advantage=normalize_advantage, seed=seed, process_group=process_group)
+        self.fused_updates = 0     # minibatches that went through learn_ops.ppo_bc_loss / ppo_bc_loss_set
+        self.labels = _check_labels(labels)
+        self.bc_coef = _check_bc_coef(bc_coef)
+
+    def set_bc_coef(self, bc_coef: float) -> None:
+        """The cross-entropy's coefficient, from the next minibatch on."""
+        self.bc_coef = _check_bc_coef(bc_coef)
+
+    def _labels(self, buf):
+        return _buffer_labels(buf, self.labels, type(self).__name__)
+
+    def update(self, buf, idx: torch.Tensor, packed: Optional[dict] = None) -> torch.Tensor:
+        """One minibatch (env-major flat ids ``idx``).  Returns the logged
+        values as a device tensor: ``PPOLearner.update``'s six (the loss with
+        the cross-entropy term), cross-entropy, accuracy, labelled share, grad
+        norm."""
+        if self.recurrent:
+            (lat_pi, lat_vf, lat_pair), src = self._evaluate_recurrent(buf, packed or self._pack_begin(buf, idx))
+        else:
+            (lat_pi, lat_vf, lat_pair), src = self._evaluate_ff(buf, idx)
+        norm = self.normalize_advantage and (self.recurrent or src.numel() > 1)
+        labels, weight = self._labels(buf)
+        pol = self.policy
+        ex = pol.mlp_extractor
+        if lat_pi.is_cuda and self.fused_loss:
+            F = ex.latent_dim_pi
+            if F == ex.latent_dim_vf and learn_ops.ppo_loss_supported(pol.action_net, pol.value_net, F):
+                h = learn_ops.mlp_pair(ex.policy_net, ex.value_net, lat_pi, None if lat_vf is lat_pi else lat_vf,
+                                       x_pair=lat_pair, stacked=True)
+                if h is not None:
+                    fused = learn_ops.ppo_bc_loss_set if self.labels == "set" else learn_ops.ppo_bc_loss
+                    dh, grads, stats = fused(h, pol.action_net, pol.value_net, src, buf.actions.reshape(-1),
+                                             buf.advantages.reshape(-1), buf.log_probs.reshape(-1),
+                                             buf.returns.reshape(-1), labels, weight, self.clip_range, self.ent_coef,
+                                             self.vf_coef, self.bc_coef, norm)
+                    self.fused_updates += 1
+                    return self._step_fused(h, dh, grads, stats)
+        # torch's ops and autograd: the CPU path, and heads the fused kernel does not take
+        h_pi, h_vf = learn_ops.mlp_pair(ex.policy_net, ex.value_net, lat_pi, None if lat_vf is lat_pi else lat_vf,
+                                        x_pair=lat_pair)
+        logits = learn_ops.linear(h_pi, pol.action_net)
+        values = learn_ops.linear(h_vf, pol.value_net).flatten()
+        A = logits.shape[-1]
+        lp_all = torch.log_softmax(logits, dim=-1)
+        log_prob = lp_all.gather(1, buf.actions.reshape(-1)[src].long().view(-1, 1)).flatten()
+        entropy = -(lp_all.exp() * lp_all).sum(-1)
+        adv = buf.advantages.reshape(-1)[src]
+        if norm:
+            adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+        old_lp = buf.log_probs.reshape(-1)[src]
+        ret = buf.returns.reshape(-1)[src]
+        ratio = torch.exp(log_prob - old_lp)
+        policy_loss = -torch.min(adv * ratio, adv * torch.clamp(ratio, 1 - self.clip_range, 1 + self.clip_range)).mean()
+        value_loss = Fn.mse_loss(ret, values)
+        entropy_loss = -entropy.mean()
+        w = torch.ones_like(values) if weight is None else (weight[src] != 0).to(values.dtype)
+        if self.labels == "set":
+            in_set = ((labels[src].long().view(-1, 1) >> torch.arange(A, device=logits.device)) & 1).bool()
+            some = in_set.any(-1)
+            w = w * some.to(w.dtype)
+            masked = logits.masked_fill(~in_set, float("-inf"))
+            masked = torch.where(some.view(-1, 1), masked, torch.zeros_like(masked))   # (an empty set: no -inf row)
+            lp = torch.logsumexp(masked, dim=-1) - torch.logsumexp(logits, dim=-1)
+        else:
+            lab = labels[src].long()
+            lp = lp_all.gather(1, lab.view(-1, 1)).flatten()
+        n = w.sum()
+        den = torch.clamp(n, min=1.0)
+        bc = (w * -lp).sum() / den
+        loss = policy_loss + self.ent_coef * entropy_loss + self.vf_coef * value_loss + self.bc_coef * bc
+        self.optimizer.zero_grad(set_to_none=True)
+        loss.backward()
+        if self.group is not None:
+            self._allreduce_grads()
+        gnorm = self._clip_step()
+        with torch.no_grad():
+            log_ratio = log_prob - old_lp
+            top = logits.max(-1, keepdim=True).values
+            ar = torch.arange(A, device=logits.device).expand_as(logits)
+            amax = torch.where(logits == top, ar, torch.full_like(ar, A)).min(-1).values   # ties: the lowest index
+            right = in_set.gather(1, amax.view(-1, 1)).flatten() if self.labels == "set" else amax == lab
+            acc = (w.double() * right.double()).sum() / den.double()
+            return torch.stack([policy_loss.detach().double(), value_loss.detach().double(),
+                                entropy_loss.detach().double(), loss.detach().double(),
+                                ((torch.exp(log_ratio) - 1) - log_ratio).mean().double(),
+                                (torch.abs(ratio - 1) > self.clip_range).double().mean(), bc.detach().double(), acc,
+                                n.double() / w.numel(), gnorm.detach().double()])
+
+    def train(self, buf, epoch_orders: Optional[Sequence] = None) -> Dict[str, float]:
+        """One ``train()`` over a ``DaggerBuffer`` collected with beta = 0
+        (n_epochs passes).  Returns ``PPOLearner.train``'s keys plus
+        ``bc_loss``, ``accuracy`` and ``labelled`` (``BCLearner.train``)."""
+        self._labels(buf)
+        took = getattr(buf, "took_expert", None)
+        if took is not None and bool(took.any()):       # one host read per rollout
+            raise ValueError(f"{type(self).__name__} needs a rollout collected with beta = 0: where the planner's "
+                             "action was executed, log_probs belong to another action (DaggerBuffer)")
+        m, n_mb = self._run_epochs(buf, epoch_orders, width=10)
+        return dict(policy_gradient_loss=m[0], value_loss=m[1], entropy_loss=m[2], loss=m[3], approx_kl=m[4],
+                    clip_fraction=m[5], bc_loss=m[6], accuracy=m[7], labelled=m[8], grad_norm=m[9],
+                    explained_variance=self._explained_variance(buf), n_minibatches=n_mb, n_updates=self.n_updates)
+
+
+def kickstart(collector: DaggerCollector, learner: KickstartLearner, total_timesteps: int,
+              bc_coef: Union[float, Callable[[int], float]] = 1.0, callback=None) -> List[Dict[str, float]]:
+    """Kickstarted PPO: ``ppo.learn``'s loop (its callbacks, Monitor,
+    exploration and reward-normaliser keys) over a ``DaggerCollector`` at
+    beta = 0 and a ``KickstartLearner``.
+
+    ``bc_coef``: the cross-entropy's coefficient, a float or
+    ``callable(iteration) -> float`` with iteration 0, 1, ... (kickstarting
+    lets it decay to 0, e.g. ``lambda i: 0.5 ** i``; at 0 the update is
+    ``PPOLearner``'s).
+
+    Returns the per-iteration rows: the train dict
+    (``KickstartLearner.train``), ``bc_coef``, ``num_timesteps`` and the keys
+    ``ppo.learn`` reports."""
+    collector.set_beta(0.0)
+
+    def begin(it):
+        c = float(bc_coef(it)) if callable(bc_coef) else float(bc_coef)
+        learner.set_bc_coef(c)
+        return {"bc_coef": c}
+
+    return run_loop(collector, learner, total_timesteps, callback, begin=begin)

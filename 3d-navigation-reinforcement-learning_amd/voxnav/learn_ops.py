@@ -212,12 +212,14 @@ def ppo_loss_supported(action_net: torch.nn.Linear, value_net: torch.nn.Linear, 
 
 
 def _head_loss(name: str, h: torch.Tensor, action_net: torch.nn.Linear, value_net: torch.nn.Linear,
-               src: Optional[torch.Tensor], buffers, what: str, scalars, adv_words: int = 0):
+               src: Optional[torch.Tensor], buffers, what: str, scalars, adv_words: int = 0,
+               n_stats: int = 6):
     """What ppo_loss, bc_loss and bc_loss_set share (csrc/head_loss.h is their one kernel): the
     checks, the workspaces, the call of ``vn_<name>`` and the views of the head gradients.
     ``buffers``: the entry point's gathered buffers as (tensor or None, dtype), in its argument
     order; ``scalars``: its arguments between the sizes and the outputs; ``adv_words``: f64
-    words of vn_ppo_loss' advantage sums, passed before the partials."""
+    words of vn_ppo_loss' advantage sums, passed before the partials; ``n_stats``: the entry
+    point's stats words."""
     lib = _native.load()
     _, M, F = h.shape
     A = action_net.out_features
@@ -230,20 +232,21 @@ def _head_loss(name: str, h: torch.Tensor, action_net: torch.nn.Linear, value_ne
     if src is not None and (src.dtype != torch.int64 or src.numel() != M or not src.is_contiguous()):
         raise ValueError(f"{name}: src must be [M] contiguous int64")
     npart, nspart = C.c_int64(), C.c_int64()
-    sizes = "vn_bc_loss_part_floats" if name.startswith("bc_") else "vn_ppo_loss_part_floats"
+    sizes = ("vn_bc_loss_part_floats" if name.startswith("bc_") else
+             "vn_ppo_bc_loss_part_floats" if name.startswith("ppo_bc_") else "vn_ppo_loss_part_floats")
     _native.check(getattr(lib, sizes)(M, F, A, C.byref(npart), C.byref(nspart)), sizes)
     dh = torch.empty((2, M, F), dtype=torch.float32, device=dev)
     gh = torch.empty(A * F + A + F + 1, dtype=torch.float32, device=dev)
-    dbl = torch.empty(6 + adv_words + nspart.value, dtype=torch.float64, device=dev)
+    dbl = torch.empty(n_stats + adv_words + nspart.value, dtype=torch.float64, device=dev)
     part = torch.empty(npart.value, dtype=torch.float32, device=dev)
-    stats = dbl[:6]
+    stats = dbl[:n_stats]
     wa, ba = action_net.weight.detach(), action_net.bias.detach()
     wv, bv = value_net.weight.detach(), value_net.bias.detach()
-    adv_sums = (_p(dbl[6:6 + adv_words]),) if adv_words else ()
+    adv_sums = (_p(dbl[n_stats:n_stats + adv_words]),) if adv_words else ()
     _native.check(getattr(lib, "vn_" + name)(_p(h[0]), _p(h[1]), F, _p(wa.contiguous()), _p(ba), _p(wv.contiguous()),
                                               _p(bv), _p(src), *[_p(t) for t, _ in buffers], M, F, A, *scalars,
                                               _p(dh[0]), _p(dh[1]), _p(gh), _p(stats), *adv_sums, _p(part),
-                                              _p(dbl[6 + adv_words:]), _stream(dev)), "vn_" + name)
+                                              _p(dbl[n_stats + adv_words:]), _stream(dev)), "vn_" + name)
     grads = (gh[:A * F].view(A, F), gh[A * F:A * F + A], gh[A * F + A:A * F + A + F].view(1, F), gh[-1:])
     return dh, grads, stats
 
@@ -303,6 +306,43 @@ def bc_loss_set(h: torch.Tensor, action_net: torch.nn.Linear, value_net: torch.n
     return _head_loss("bc_loss_set", h, action_net, value_net, src,
                       ((label_set, torch.uint8), (weight, torch.uint8), (returns, torch.float32)),
                       "uint8 label sets / uint8 weights / f32 returns", (float(ent_coef), float(vf_coef)))
+
+
+def _ppo_bc(name, h, action_net, value_net, src, actions, advantages, old_log_prob, returns, labels, label_dtype,
+            weight, clip_range, ent_coef, vf_coef, bc_coef, normalize_advantage):
+    return _head_loss(name, h, action_net, value_net, src,
+                      ((actions, torch.int32), (advantages, torch.float32), (old_log_prob, torch.float32),
+                       (returns, torch.float32), (labels, label_dtype), (weight, torch.uint8)),
+                      "int32 actions / f32 values / labels / uint8 weights",
+                      (float(clip_range), float(ent_coef), float(vf_coef), float(bc_coef),
+                       int(bool(normalize_advantage))), adv_words=128, n_stats=9)
+
+
+def ppo_bc_loss(h: torch.Tensor, action_net: torch.nn.Linear, value_net: torch.nn.Linear, src: Optional[torch.Tensor],
+                actions: torch.Tensor, advantages: torch.Tensor, old_log_prob: torch.Tensor, returns: torch.Tensor,
+                labels: torch.Tensor, weight: Optional[torch.Tensor], clip_range: float, ent_coef: float,
+                vf_coef: float, bc_coef: float, normalize_advantage: bool):
+    """Kickstarted PPO's minibatch loss and its gradient
+    (csrc/voxnav_ppo_bc_loss.hip, the formula in include/voxnav.h
+    vn_ppo_bc_loss): ``ppo_loss`` + ``bc_coef`` x the cross-entropy of
+    ``bc_loss`` to ``labels`` (int32) over the samples with ``weight`` (uint8,
+    or None), in one pass over the samples.  Arguments and outputs as
+    ``ppo_loss``; stats f64 [9]: its six (the loss with the cross-entropy
+    term), then cross-entropy, accuracy, labelled share."""
+    return _ppo_bc("ppo_bc_loss", h, action_net, value_net, src, actions, advantages, old_log_prob, returns, labels,
+                   torch.int32, weight, clip_range, ent_coef, vf_coef, bc_coef, normalize_advantage)
+
+
+def ppo_bc_loss_set(h: torch.Tensor, action_net: torch.nn.Linear, value_net: torch.nn.Linear,
+                    src: Optional[torch.Tensor], actions: torch.Tensor, advantages: torch.Tensor,
+                    old_log_prob: torch.Tensor, returns: torch.Tensor, label_set: torch.Tensor,
+                    weight: Optional[torch.Tensor], clip_range: float, ent_coef: float, vf_coef: float, bc_coef: float,
+                    normalize_advantage: bool):
+    """``ppo_bc_loss`` with the set-valued cross-entropy of ``bc_loss_set``
+    (``vn_ppo_bc_loss_set``): ``label_set`` uint8, a sample with an empty set is
+    unlabelled, accuracy counts the argmax lying in the set."""
+    return _ppo_bc("ppo_bc_loss_set", h, action_net, value_net, src, actions, advantages, old_log_prob, returns,
+                   label_set, torch.uint8, weight, clip_range, ent_coef, vf_coef, bc_coef, normalize_advantage)
 
 
 def grad_norm_scale(params, max_norm: float, work: Optional[torch.Tensor] = None):

@@ -416,16 +416,18 @@ class PPOLearner:
         return torch.stack(logs)
 
     # ------------------------------------------------------------ train
-    def train(self, buf, epoch_orders: Optional[Sequence] = None) -> Dict[str, float]:
-        """One ``train()`` over a collector ``RolloutBuffer`` (n_epochs passes).
-        Returns the means of sb3's logged quantities."""
+    def _run_epochs(self, buf, epoch_orders: Optional[Sequence], width: int = 7):
+        """``train()``'s passes over the buffer (this class's and its subclasses'): per
+        epoch the rolled (recurrent) or permuted env-major order cut into minibatches of
+        ``batch_size``, through ``update_many``.  ``width``: the length of ``update``'s log
+        vector.  -> (the logs' means over the minibatches, the minibatch count)."""
         T, N = buf.actions.shape
         total = T * N
         dev = buf.actions.device
         if self.recurrent and (buf.lstm_h is None or buf.lstm_c is None):
             raise ValueError("the recurrent learner needs the buffer's LSTM states (store_lstm_states=True)")
         orders = list(epoch_orders) if epoch_orders is not None else self._orders(total)
-        acc = torch.zeros(7, dtype=torch.float64, device=dev)
+        acc = torch.zeros(width, dtype=torch.float64, device=dev)
         n_mb = 0
         self.policy.train()
         for order in orders:
@@ -437,14 +439,22 @@ class PPOLearner:
                                     windows=self.recurrent)
             acc += logs.sum(0)
             n_mb += logs.shape[0]
-        m = (acc / max(1, n_mb)).tolist()
+        return (acc / max(1, n_mb)).tolist(), n_mb
+
+    @staticmethod
+    def _explained_variance(buf) -> float:
         with torch.no_grad():
             v, r = buf.values.reshape(-1), buf.returns.reshape(-1)
             var_r = torch.var(r)
-            ev = float("nan") if float(var_r) == 0 else float(1 - torch.var(r - v) / var_r)
+            return float("nan") if float(var_r) == 0 else float(1 - torch.var(r - v) / var_r)
+
+    def train(self, buf, epoch_orders: Optional[Sequence] = None) -> Dict[str, float]:
+        """One ``train()`` over a collector ``RolloutBuffer`` (n_epochs passes).
+        Returns the means of sb3's logged quantities."""
+        m, n_mb = self._run_epochs(buf, epoch_orders)
         return dict(policy_gradient_loss=m[0], value_loss=m[1], entropy_loss=m[2], loss=m[3], approx_kl=m[4],
-                    clip_fraction=m[5], grad_norm=m[6], explained_variance=ev, n_minibatches=n_mb,
-                    n_updates=self.n_updates)
+                    clip_fraction=m[5], grad_norm=m[6], explained_variance=self._explained_variance(buf),
+                    n_minibatches=n_mb, n_updates=self.n_updates)
 
 
 def _ranks_share_device(group, params) -> bool:
@@ -484,12 +494,21 @@ def learn(collector, learner: PPOLearner, total_timesteps: int, callback=None) -
     ``EpisodeMonitor._harvest_exploration``) -- and the evaluation's
     ``eval/*`` keys when one ran; with a reward normaliser on the collector
     (``voxnav.normalize``) its running ``ret_rms_var`` / ``ret_rms_mean``."""
+    return run_loop(collector, learner, total_timesteps, callback)
+
+
+def run_loop(collector, learner, total_timesteps: int, callback=None, begin=None, extra=None):
+    """The loop of ``learn`` (and of ``imitate.warm_start`` / ``imitate.kickstart``, which
+    add a schedule): ``begin(iteration)`` runs before each rollout (iteration 0, 1, ...)
+    and ``extra(buf)`` after each update; the dicts they return go into the iteration's
+    row between the train stats and the Monitor keys."""
     if collector.policy is not learner.policy:
         raise ValueError("collector and learner must share the policy module")
     cbs = [] if callback is None else (list(callback) if isinstance(callback, (list, tuple)) else [callback])
     per_rollout = collector.n_steps * collector.N
     done, it, history = 0, 0, []
     while done < total_timesteps:
+        row = dict(begin(it) or {}) if begin is not None else {}
         buf = collector.collect()
         done += per_rollout
         it += 1
@@ -499,7 +518,10 @@ def learn(collector, learner: PPOLearner, total_timesteps: int, callback=None) -
                 evals.update(cb.on_rollout_end(learner.policy, done, collector.n_steps, learner.optimizer) or {})
         st = learner.train(buf)
         collector.sync_weights()
+        st.update(row)
         st["num_timesteps"] = done
+        if extra is not None:
+            st.update(extra(buf) or {})
         mon = getattr(collector, "monitor", None)
         if mon is not None and mon.ep_info_buffer:
             st["ep_rew_mean"] = mon.ep_rew_mean()

@@ -993,6 +993,57 @@ int vn_bc_loss_set(const float *hp, const float *hv, int64_t ldh, const float *w
                    const float *returns, int32_t M, int32_t F, int32_t A, float ent_coef, float vf_coef, float *dhp,
                    float *dhv, float *grad_heads, double *stats, float *part, double *spart, void *stream);
 
+/* Kickstarted PPO's minibatch loss + its gradient to the MLP latents
+ * (csrc/voxnav_ppo_bc_loss.hip): vn_ppo_loss with the cross-entropy of
+ * vn_bc_loss (labels) / vn_bc_loss_set (label_set) added under bc_coef, in one
+ * pass over the samples.  lp, p, H, v as above; A_i the (optionally
+ * normalised) advantage, r_i the ratio and g_lp,i the surrogate's gradient
+ * scale of vn_ppo_loss; w_i, n, q_i and ce_i those of vn_bc_loss /
+ * vn_bc_loss_set (q_i one-hot at the label, or the softmax of z_i restricted to
+ * S_i = label_set_i & (2^A - 1); n the labelled count, with sets only samples
+ * with S_i != 0):
+ *   loss  = -mean(min(A r, A clamp(r, 1-c, 1+c))) - ent_coef mean(H) + vf_coef mean((ret - v)^2)
+ *           + bc_coef (1/max(n,1)) sum_i w_i ce_i
+ *   dz_ij = g_lp,i ([j = a_i] - p_ij) + bc_coef (w_i / max(n,1)) (p_ij - q_ij) + (ent_coef / M) p_ij (lp_ij + H_i)
+ *   dv_i  = 2 vf_coef (v_i - ret_i) / M
+ * dz is formed as (ppo term + bc term) + entropy term: with bc_coef = 0, or
+ * with no labelled sample, dhp, dhv, grad_heads and stats[0..5] equal
+ * vn_ppo_loss's as values; with all advantages 0, normalize_advantage = 0,
+ * finite ratios and bc_coef = 1, dhp, dhv and grad_heads equal vn_bc_loss's
+ * (vn_bc_loss_set's).  With n = 0 the cross-entropy, its gradient and the
+ * accuracy are exactly 0.
+ *   the arguments of vn_ppo_loss, and labels int32 / label_set uint8, weight
+ *   uint8 (NULL: every sample labelled), indexed by src like the other buffers
+ *   -> dhp, dhv, grad_heads as vn_ppo_loss; stats [9] f64: [0..5] as
+ *      vn_ppo_loss, with [3], the loss, including bc_coef ce; [6] the
+ *      cross-entropy, [7] the accuracy (labelled samples whose argmax is the
+ *      label / lies in the set, over max(n,1)), [8] n / M.  adv_sums [128] f64
+ *      scratch; part / spart: workspaces of the sizes
+ *      vn_ppo_bc_loss_part_floats returns (floats / 8-byte words: the blocks'
+ *      seven f64 sums and the 64 labelled-count words behind them).
+ * Up to four launches (the advantage sums when normalize_advantage, the
+ * labelled count with weights or sets, the samples, the fixed-order sum);
+ * stream-ordered, no host synchronisation, plain stores: two calls on the same
+ * inputs give the same bits.
+ * VN_ERR_INVALID, with nothing launched: a NULL pointer other than src and
+ * weight; M < 1; A outside 1..8; F outside 64..256 or no multiple of 64;
+ * ldh < F; bc_coef negative or not finite.  clip_range is taken as vn_ppo_loss
+ * takes it.  vn_ppo_bc_loss_part_floats: M, F or A < 1. */
+int vn_ppo_bc_loss_part_floats(int32_t M, int32_t F, int32_t A, int64_t *n_part, int64_t *n_spart);
+int vn_ppo_bc_loss(const float *hp, const float *hv, int64_t ldh, const float *wa, const float *ba, const float *wv,
+                   const float *bv, const int64_t *src, const int32_t *actions, const float *advantages,
+                   const float *old_log_prob, const float *returns, const int32_t *labels, const uint8_t *weight,
+                   int32_t M, int32_t F, int32_t A, float clip_range, float ent_coef, float vf_coef, float bc_coef,
+                   int32_t normalize_advantage, float *dhp, float *dhv, float *grad_heads, double *stats,
+                   double *adv_sums, float *part, double *spart, void *stream);
+int vn_ppo_bc_loss_set(const float *hp, const float *hv, int64_t ldh, const float *wa, const float *ba,
+                       const float *wv, const float *bv, const int64_t *src, const int32_t *actions,
+                       const float *advantages, const float *old_log_prob, const float *returns,
+                       const uint8_t *label_set, const uint8_t *weight, int32_t M, int32_t F, int32_t A,
+                       float clip_range, float ent_coef, float vf_coef, float bc_coef, int32_t normalize_advantage,
+                       float *dhp, float *dhv, float *grad_heads, double *stats, double *adv_sums, float *part,
+                       double *spart, void *stream);
+
 /* DAgger's executed action for one collector step (csrc/voxnav_bc_loss.hip):
  * per agent i of N, with the planner's proposal expert[i] / dist[i]
  * (vn_plan_frontier) and the policy's own sample policy[i],

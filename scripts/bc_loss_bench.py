@@ -9,8 +9,22 @@ The BC kernel does strictly less (no advantage pass without weights, two fewer g
 so it should not be slower; the bound is 1.15 x the vn_ppo_loss median of the same run, the
 10-15 % placement noise of DESIGN.md 7.  vn_bc_loss_set (always counted, a second softmax over the
 set) is timed beside them and its ratio reported, not bounded.  --lib PATH runs another build of
-the library (A/B against a parent build).  Prints one JSON line; exit status 1 when a ratio
-exceeds the bound.  Needs a GPU."""
+the library (A/B against a parent build).
+
+Kickstarted PPO (csrc/voxnav_ppo_bc_loss.hip, a library that has it): ppo_bc_loss and
+ppo_bc_loss_set (normalised advantages, with weights) are timed beside their two-call alternative
+on the same tensors -- vn_ppo_loss, then vn_bc_loss (or _set) with ent_coef = vf_coef = 0, then the
+gradient adds (dhp, dhv, the action head's pair, the value head's pair: four calls).  --rounds R
+times the whole case list R times in turn (interleaved); each case then carries its R medians, and
+``kickstart`` reports per width and label form the fused call's gain over the alternative next to
+the alternative's own max - min spread over the rounds: fusing has a case only where the gain
+exceeds that spread.  The fused call against vn_ppo_loss alone is reported without a bound.
+The events bracket the host's enqueue of a call: at --batch 1 (the protocol above) a case of ~0.1 ms
+includes the gaps between its launches, and the alternative has about seven launches more than the
+fused call; --batch B puts B calls between one pair of events, so the queue stays full and the
+figure is device time per call.
+
+Prints one JSON line; exit status 1 when a bounded ratio exceeds the bound.  Needs a GPU."""
 import argparse
 import json
 import statistics
@@ -22,13 +36,14 @@ sys.path.insert(0, str(REPO / "3d-navigation-reinforcement-learning_amd"))
 import torch  # noqa: E402
 
 from voxnav import _native  # noqa: E402
-from voxnav.learn_ops import bc_loss, bc_loss_set, ppo_loss  # noqa: E402
+from voxnav.learn_ops import bc_loss, bc_loss_set, ppo_bc_loss, ppo_bc_loss_set, ppo_loss  # noqa: E402
 
 BOUND = 1.15
 
 
-def timed(fn, reps, warmup, dev):
-    """Median / min / max device milliseconds of fn() over `reps` calls after `warmup`."""
+def timed(fn, reps, warmup, dev, batch=1):
+    """Median / min / max device milliseconds of fn() over `reps` timed repetitions after `warmup`;
+    a repetition is `batch` calls back to back between one pair of events, divided by `batch`."""
     stream = torch.cuda.current_stream(dev)
     for _ in range(warmup):
         fn()
@@ -37,10 +52,11 @@ def timed(fn, reps, warmup, dev):
     for _ in range(reps):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record(stream)
-        fn()
+        for _ in range(batch):
+            fn()
         b.record(stream)
         torch.cuda.synchronize(dev)
-        ms.append(a.elapsed_time(b))
+        ms.append(a.elapsed_time(b) / batch)
     return {"median_ms": round(statistics.median(ms), 4), "min_ms": round(min(ms), 4), "max_ms": round(max(ms), 4)}
 
 
@@ -51,6 +67,10 @@ def main():
     ap.add_argument("--widths", type=int, nargs="+", default=[128, 256])
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=1, help="time the whole case list this many times in turn")
+    ap.add_argument("--bc-coef", type=float, default=0.5)
+    ap.add_argument("--batch", type=int, default=1,
+                    help="calls per timed repetition: above 1 the queue stays full and host enqueue gaps drop out")
     ap.add_argument("--lib", type=Path, default=None, help="run this build of libvoxnav.so")
     args = ap.parse_args()
     if args.lib is not None:
@@ -66,8 +86,20 @@ def main():
     adv, olp, ret = torch.randn(R, device=dev), torch.randn(R, device=dev) - 1.8, torch.randn(R, device=dev)
     wgt = (torch.rand(R, device=dev) < 0.9).to(torch.uint8)
     sets = ((1 << act) | torch.randint(0, 1 << A, (R,), device=dev)).to(torch.uint8)   # the label and random others
+    kick = hasattr(_native.load(), "vn_ppo_bc_loss")
+    bc_coef = args.bc_coef
+
+    def two_call(bc, labels, h, an, vn):
+        dh, grads, stats = ppo_loss(h, an, vn, src, act, adv, olp, ret, 0.2, 0.01, 0.5, True)
+        bdh, bgrads, _ = bc(h, an, vn, src, labels, wgt, ret, 0.0, 0.0)
+        dh[0].add_(bdh[0], alpha=bc_coef)
+        dh[1].add_(bdh[1], alpha=bc_coef)
+        torch._foreach_add_(list(grads[:2]), list(bgrads[:2]), alpha=bc_coef)
+        torch._foreach_add_(list(grads[2:]), list(bgrads[2:]), alpha=bc_coef)
+        return dh, grads, stats
+
     res = {"lib": None if args.lib is None else str(args.lib), "M": M, "A": A, "reps": args.reps,
-           "warmup": args.warmup, "bound": BOUND, "widths": {}}
+           "warmup": args.warmup, "rounds": args.rounds, "batch": args.batch, "bound": BOUND, "widths": {}}
     ok = True
     for F in args.widths:
         an, vn = torch.nn.Linear(F, A).to(dev), torch.nn.Linear(F, 1).to(dev)
@@ -78,7 +110,33 @@ def main():
             "bc_loss_weights": lambda: bc_loss(h, an, vn, src, act, wgt, ret, 0.0, 0.5),
             "bc_loss_set": lambda: bc_loss_set(h, an, vn, src, sets, wgt, ret, 0.0, 0.5),
         }
-        r = {name: timed(fn, args.reps, args.warmup, dev) for name, fn in cases.items()}
+        if kick:
+            cases.update({
+                "ppo_bc_loss": lambda: ppo_bc_loss(h, an, vn, src, act, adv, olp, ret, act, wgt, 0.2, 0.01, 0.5, bc_coef,
+                                                   True),
+                "two_call": lambda: two_call(bc_loss, act, h, an, vn),
+                "ppo_bc_loss_set": lambda: ppo_bc_loss_set(h, an, vn, src, act, adv, olp, ret, sets, wgt, 0.2, 0.01, 0.5,
+                                                           bc_coef, True),
+                "two_call_set": lambda: two_call(bc_loss_set, sets, h, an, vn),
+            })
+        rounds = [{name: timed(fn, args.reps, args.warmup, dev, args.batch) for name, fn in cases.items()}
+                  for _ in range(args.rounds)]
+        r = rounds[0]
+        if args.rounds > 1:
+            for name in cases:
+                r[name]["rounds_median_ms"] = [x[name]["median_ms"] for x in rounds]
+        if kick:
+            for fused, alt in (("ppo_bc_loss", "two_call"), ("ppo_bc_loss_set", "two_call_set")):
+                fm = [x[fused]["median_ms"] for x in rounds]
+                am = [x[alt]["median_ms"] for x in rounds]
+                pm = [x["ppo_loss"]["median_ms"] for x in rounds]
+                gain, spread = statistics.median(am) - statistics.median(fm), max(am) - min(am)
+                r[fused]["kickstart"] = {
+                    "fused_ms": round(statistics.median(fm), 4), "two_call_ms": round(statistics.median(am), 4),
+                    "gain_ms": round(gain, 4), "two_call_spread_ms": round(spread, 4),
+                    "speedup": round(statistics.median(am) / statistics.median(fm), 4),
+                    "gain_exceeds_spread": bool(gain > spread),
+                    "ratio_to_ppo_loss": round(statistics.median(fm) / statistics.median(pm), 4)}
         for name in ("bc_loss", "bc_loss_weights", "bc_loss_set"):
             r[name]["ratio_to_ppo_loss"] = round(r[name]["median_ms"] / r["ppo_loss"]["median_ms"], 4)
             ok = ok and (name == "bc_loss_set" or r[name]["ratio_to_ppo_loss"] <= BOUND)

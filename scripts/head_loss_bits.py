@@ -10,7 +10,12 @@ weights).  Per call one sha256 of each output's bytes: dh, the four head gradien
 
   python scripts/head_loss_bits.py --lib PATH/libvoxnav.so --out bits.json
 
-Needs a GPU; the whole run takes seconds."""
+Needs a GPU; the whole run takes seconds.
+
+  python scripts/head_loss_bits.py --summarise A.json B.json --out summary.json
+
+writes, without a GPU, the two files' sizes and sha256 and whether they are identical (what is
+kept in profiles/ in place of the files themselves)."""
 import argparse
 import hashlib
 import json
@@ -40,9 +45,25 @@ def digests(out):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--lib", type=Path, required=True, help="the build of libvoxnav.so to run")
+    ap.add_argument("--lib", type=Path, default=None, help="the build of libvoxnav.so to run")
+    ap.add_argument("--summarise", type=Path, nargs=2, default=None, metavar=("A", "B"),
+                    help="compare two outputs of this script instead of running")
     ap.add_argument("--out", type=Path, default=None, help="write the JSON here (default: stdout)")
     args = ap.parse_args()
+    if args.summarise is not None:
+        data = [f.read_bytes() for f in args.summarise]
+        cases = json.loads(data[0])
+        text = json.dumps({"cases": len(cases), "calls": sum(len(v) for v in cases.values()),
+                           "digests_per_call": len(NAMES), "bytes": [len(d) for d in data],
+                           "sha256": [hashlib.sha256(d).hexdigest() for d in data],
+                           "identical": data[0] == data[1]}, indent=1)
+        if args.out is None:
+            print(text)
+        else:
+            args.out.write_text(text + "\n")
+        return 0 if data[0] == data[1] else 1
+    if args.lib is None:
+        ap.error("--lib is required")
     _native.use_library(args.lib.resolve())
     if not torch.cuda.is_available():
         raise SystemExit("head_loss_bits.py needs a GPU")

@@ -7,8 +7,13 @@ The policy is the reference's (``--policy lstm``: RecurrentActorCriticPolicy, LS
 [256, 256, 128]; ``mlp``: ActorCriticPolicy with the same MLP).  beta falls linearly from 1 by
 --beta-step per iteration down to --beta-min.  --episodes agents per evaluation, agent i reset with
 seed + i, one deterministic episode each, L 10.  --labels set trains on the planner's set of equally
-short actions (vn_plan_frontier_dists, vn_bc_loss_set) instead of its lowest-k action.  Prints the per-iteration rows, the table and one
-JSON line.  Needs a GPU."""
+short actions (vn_plan_frontier_dists, vn_bc_loss_set) instead of its lowest-k action.
+
+--then ppo | kickstart --then-iterations K: after the warm start, K more iterations
+on the same collector at beta = 0 with a fresh learner of the reference's PPO hyperparameters --
+plain ``ppo.learn``, or ``imitate.kickstart`` with bc_coef = --bc-decay ^ iteration -- and one more
+table row for the policy after them.  Prints the per-iteration rows, the table and one JSON line.
+Needs a GPU."""
 import argparse
 import json
 import sys
@@ -21,9 +26,10 @@ import torch  # noqa: E402
 
 from voxnav.env import BatchedGridEnv  # noqa: E402
 from voxnav.evaluate import RESULTS_HEADER, evaluate_policy, results_table_row  # noqa: E402
-from voxnav.imitate import BCLearner, DaggerCollector, warm_start  # noqa: E402
+from voxnav.imitate import BCLearner, DaggerCollector, KickstartLearner, kickstart, warm_start  # noqa: E402
 from voxnav.normalize import RewardNormalizer  # noqa: E402
 from voxnav.planner import evaluate_planner  # noqa: E402
+from voxnav.ppo import PPOLearner, learn  # noqa: E402
 from voxnav.policy import ActorCriticPolicy, RecurrentActorCriticPolicy  # noqa: E402
 from voxnav.rooms import load_archive_set  # noqa: E402
 
@@ -49,6 +55,10 @@ def main():
                     help="set: the planner's set of equally short actions as the label (DESIGN.md 10.5)")
     ap.add_argument("--norm-reward", action="store_true",
                     help="VecNormalize(norm_reward=True) on the rollout's rewards (DESIGN.md 10.6)")
+    ap.add_argument("--then", choices=["ppo", "kickstart"], default=None,
+                    help="after the warm start: plain PPO, or PPO with the decaying cross-entropy (DESIGN.md 10.7)")
+    ap.add_argument("--then-iterations", type=int, default=8)
+    ap.add_argument("--bc-decay", type=float, default=0.7, help="kickstart: bc_coef = bc_decay ^ iteration")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("warm_start_eval.py needs a GPU")
@@ -76,16 +86,40 @@ def main():
                       beta=lambda i: max(args.beta_min, 1.0 - args.beta_step * i), callback=show)
     torch.cuda.synchronize()
     train_s = time.time() - t0
+    tag = (" (set labels)" if args.labels == "set" else "") + (" (normalised rewards)" if args.norm_reward else "")
+    rows["warm-started policy" + tag] = evaluate_policy(pol, eval_rooms, **kw)
+    then_hist, then_s = [], 0.0
+    if args.then is not None:
+        def show_then(it, done, st):
+            keys = ("bc_coef", "loss", "policy_gradient_loss", "value_loss", "entropy_loss", "approx_kl", "bc_loss",
+                    "accuracy", "grad_norm", "ep_finished_rate", "ep_bumps_mean", "ep_coverage", "ret_rms_var")
+            print(f"{args.then} iter {it:3d} steps {done:9d} " + " ".join(f"{k}={st[k]:.4g}" for k in keys if k in st),
+                  flush=True)
+
+        col.set_beta(0.0)
+        steps = args.then_iterations * args.agents * args.n_steps
+        hyper = dict(learning_rate=args.lr, n_epochs=args.epochs, batch_size=args.batch, vf_coef=args.vf_coef,
+                     seed=args.seed)
+        t1 = time.time()
+        if args.then == "kickstart":
+            kl = KickstartLearner(pol, labels=args.labels, **hyper)
+            then_hist = kickstart(col, kl, total_timesteps=steps, bc_coef=lambda i: args.bc_decay ** i,
+                                  callback=show_then)
+            print(f"kickstart: fused loss minibatches {kl.fused_updates} of {kl.n_updates}")
+        else:
+            then_hist = learn(col, PPOLearner(pol, **hyper), total_timesteps=steps, callback=show_then)
+        torch.cuda.synchronize()
+        then_s = time.time() - t1
+        rows[f"warm start, then {args.then_iterations} x {args.then}" + tag] = evaluate_policy(pol, eval_rooms, **kw)
     env.close()
-    rows["warm-started policy" + (" (set labels)" if args.labels == "set" else "")
-         + (" (normalised rewards)" if args.norm_reward else "")] = evaluate_policy(pol, eval_rooms, **kw)
     rows["frontier planner"] = evaluate_planner(eval_rooms, **kw)
     print(f"warm start: {len(hist)} iterations, {hist[-1]['num_timesteps']} env steps, {train_s:.1f} s "
           f"(fused loss minibatches: {ln.fused_updates} of {ln.n_updates})")
     print(RESULTS_HEADER)
     for label, r in rows.items():
         print(results_table_row(f"{args.eval_set}: {label}", r))
-    print(json.dumps(dict(args=vars(args), train_seconds=train_s, history=hist,
+    print(json.dumps(dict(args=vars(args), train_seconds=train_s, history=hist, then_seconds=then_s,
+                          then_history=then_hist,
                           table={k: {a: b for a, b in r.items() if a != "episodes"} for k, r in rows.items()})))
 
 
