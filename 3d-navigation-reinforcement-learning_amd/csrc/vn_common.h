@@ -24,8 +24,7 @@
     defined(VN_MIN_WAVES_PER_SIMD) || defined(VN_LF_ROWS) || defined(VN_LF_KC) || defined(VN_LF_RAW_BARRIER) || \
     defined(VN_LF_MIN_WAVES) || defined(VN_LF_WPE) || defined(VN_PF_FAST) || defined(VN_PF_PREF) || \
     defined(VN_ENV_WT) || defined(VN_DFLUSH_DEFAULT) || defined(VN_WIMG_REP) || \
-    defined(VN_BRICK_T) || defined(VN_WREC_K_DEFAULT) || defined(VN_GEMM_ASM) || defined(VN_ROWS_RAWBAR) || \
-    defined(VN_ROWS_PRELOAD) || defined(VN_ROWS_FLAGS)
+    defined(VN_BRICK_T) || defined(VN_WREC_K_DEFAULT) || defined(VN_GEMM_ASM) || defined(VN_ROWS_DIAG)
 #error "compile-time knobs are for the diagnostics build only (define VN_DIAG)"
 #endif
 #endif

@@ -12,11 +12,26 @@
 // run of whole sb3 sequences laid end to end, and the outputs equal sb3's
 // padded per-sequence re-run without any padding.
 //
-// Work split: block (LSTM l, unit block ub of 32 units, row tile rt of 32
-// rows); the 8 unit blocks of one (l, rt) form a group that exchanges h each
-// step.  Every block of the grid (2 x 8 x R/32 <= 256, one per CU) is
-// resident for the whole launch (checked on the host), and the hand-off is
-// the agent-scope protocol of the HIP guide's Guideline 16 (R1, counter form):
+// Work split: block (LSTM l, unit block ub, row tile rt of 32 rows); the unit
+// blocks of one (l, rt) form a group that exchanges h each step.  Two layouts
+// of the unit blocks:
+//   32 units (8 blocks per group, v_mfma_f32_32x32x2_f32): a grid of
+//     2 x 8 x R/32 blocks, one per CU at 512 rows.  Forward only, and only
+//     where the 16-unit grid would need two blocks per CU: two co-resident
+//     forwards run their steps in phase and share the SIMDs (9.4 vs 9.9 us
+//     per step at 512 rows).
+//   16 units (16 blocks per group, v_mfma_f32_16x16x4_f32): 2 x 16 x R/32
+//     blocks.  The forward up to one block per CU (6.8 vs 9.4 us per step at
+//     256 rows), and the one backward at every size (14.8 vs 15.4 us at 512
+//     rows, 10.5 vs 14.9 at 256).
+// The pick is rows_fwd_v2 (by grid size against the CU count).  The cell and
+// the counter add are said once for both forwards; their x staging, h-row
+// fetch, start-state substitution and start flags stay written out in each:
+// as functions, in every form tried, they moved registers or instructions of
+// kernels that sit at the 256-VGPR cap.
+// Every block of a grid is resident for the whole launch (checked on the
+// host, rows_grid_ok), and the hand-off is the agent-scope protocol of the
+// HIP guide's Guideline 16 (R1, counter form):
 // the payload (h_t; in the backward the partial dh of step t-1) is written
 // with 16-B write-through (sc1) stores, every storing wave drains vmcnt, the
 // block synchronises, ONE lane adds to the group's counter (agent scope); a
@@ -24,16 +39,16 @@
 // with sc1 loads only.  Spins are bounded: a timeout sets *err and the launch
 // runs to its end (the host raises).
 //
-// forward   wave w = gate w: the 32 x 32 tile [x_t | h_{t-1}] @ W[gate w, 32
-//           units]^T on v_mfma_f32_32x32x2_f32, W (168 VGPRs) resident; the
+// forward   (32 units; the 16-unit one halves the tile) wave w = gate w: the
+//           32 x 32 tile [x_t | h_{t-1}] @ W[gate w, 32 units]^T, W (168 VGPRs) resident; the
 //           x part runs while the group's h_{t-1} is still being produced;
 //           the cell (i, f, g, o, c, h) as the epilogue, c carried in
 //           registers (a block owns its units' cells).
-// backward  per step in reverse: dh = dh_out + sum of the 8 partials of step
+// backward  per step in reverse: dh = dh_out + sum of the 16 partials of step
 //           t+1 (fixed order), the cell backward (dG_t, dc carried in
-//           registers), then this block's partial dh_{t-1} = dG_t[:, its 128
+//           registers), then this block's partial dh_{t-1} = dG_t[:, its 64
 //           gate columns] @ W_hh[those rows, 256 units] (W_hh slice resident,
-//           128 VGPRs); rows whose step t starts a sequence pass no gradient
+//           64 VGPRs); rows whose step t starts a sequence pass no gradient
 //           back (their h_{t-1}, c_{t-1} came from the buffer).
 // f32 throughout (the reference's dtype); the nonlinearities on the hardware exp / rcp.
 
@@ -113,29 +128,57 @@ __device__ __forceinline__ bool wait_ge(uint32_t *cnt, uint32_t target, int32_t 
 // in front of the step's partial-dh loads -- one more memory round trip on the
 // recurrence of the block that arrives last.  Those rows are waited for
 // explicitly where they are read.
-#ifndef VN_ROWS_RAWBAR
-#define VN_ROWS_RAWBAR 1
-#endif
-#ifndef VN_ROWS_PRELOAD
-#define VN_ROWS_PRELOAD 1
-#endif
-#ifndef VN_ROWS_FLAGS
-#define VN_ROWS_FLAGS 1
-#endif
-__device__ __forceinline__ void lds_barrier() {
-#if VN_ROWS_RAWBAR
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-#else
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// after this block's payload stores, every storing wave having drained them:
+// the block barrier orders every wave's drain before the one add.  The forward
+// calls this form: it drains right behind its payload store, in front of the
+// step's 7 result stores, which the group does not wait for
+__device__ __forceinline__ void publish_drained(uint32_t *cnt) {
     __syncthreads();
-#endif
+    if (threadIdx.x == 0) __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // after this block's payload stores: drain (every wave), block barrier, one add
 __device__ __forceinline__ void publish(uint32_t *cnt) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    publish_drained(cnt);
 }
+
+// the cell of one unit from its four pre-activations and c_{t-1}
+__device__ __forceinline__ void cell_fwd(float pi, float pf, float pg, float po, float cp, float &ig, float &fg,
+                                         float &gg, float &og, float &cn, float &hn) {
+    ig = sigm(pi);
+    fg = sigm(pf);
+    gg = tanh_fast(pg);
+    og = sigm(po);
+    const float fc = fg * cp, in = ig * gg;
+    cn = fc + in;
+    hn = og * tanh_fast(cn);
+}
+
+// the cell backward of one unit: the four gate gradients of step t from dh_t
+// and the carried dc, which becomes dc_{t-1}
+__device__ __forceinline__ void cell_bwd(float dh, float ig, float fg, float gg, float og, float cp, float cn,
+                                         float &dc, float &dgi, float &dgf, float &dgg, float &dgo) {
+    const float tc = tanh_fast(cn);
+    const float dtc = dh * og;
+    const float dcc = dc + dtc * (1.0f - tc * tc);
+    dgi = dcc * gg * (ig * (1.0f - ig));
+    dgf = dcc * cp * (fg * (1.0f - fg));
+    dgg = dcc * ig * (1.0f - gg * gg);
+    dgo = dh * tc * (og * (1.0f - og));
+    dc = dcc * fg;
+}
+
+// Diagnostics build (scripts/build_variants.py rowsdiag:VN_ROWS_DIAG=1, read by
+// scripts/rows_diag.py): the 16-unit forward records each block's HW_ID /
+// XCC_ID in diag[2 b], diag[2 b + 1] and the 100-MHz clock at 7 points of its
+// step t in diag[2 grid + (b L + t) 8 + k], into the buffer that
+// vn_lstm_rows_set_diag names (NULL: off).
+#ifndef VN_ROWS_DIAG
+#define VN_ROWS_DIAG 0
+#endif
 
 struct RowsFwd {
     const float *x;          // [L][B][D]
@@ -156,7 +199,9 @@ struct RowsFwd {
     int64_t n_env;
     int L, B, NT;
     int prio;                // 16-unit layout: issue priority on the hand-off path (VN_OPT_ROWS_PRIO)
-    uint32_t *diag;          // diagnostics (NULL): placement + per-step clocks
+#if VN_ROWS_DIAG
+    uint32_t *diag;          // placement + per-step clocks (NULL: off)
+#endif
 };
 
 template <int D, int H>
@@ -229,7 +274,6 @@ __global__ __launch_bounds__(256, 1) void lstm_rows_fwd_kernel(RowsFwd a) {
     }
     __syncthreads();
 
-#if VN_ROWS_FLAGS
     // the tile's sequence-start flags, double-buffered: step t reads stf[t & 1];
     // step t + 1's are loaded at the top of step t and written to LDS after the
     // step's h loads (whose wait completes them).  Consumed at the top of the
@@ -238,20 +282,10 @@ __global__ __launch_bounds__(256, 1) void lstm_rows_fwd_kernel(RowsFwd a) {
     __shared__ uint8_t stf2[2][RW];
     if (tid < RW) stf2[0][tid] = row0 + tid < B ? 1 : 0;   // step 0: every row starts
     const int frow = min(row0 + (tid & (RW - 1)), B - 1);
-#else
-    __shared__ uint8_t stf[RW];       // the tile's sequence-start flags of the step
-    // loaded a step ahead (a load consumed in the same step stalled the x part)
-    uint8_t st_next = (tid < RW && row0 + tid < B) ? 1 : 0;
-#endif
     for (int t = 0; t < L; ++t) {
         const int xb = t & 1;
-#if VN_ROWS_FLAGS
         const uint8_t *stf = stf2[t & 1];
         const uint8_t st_ld = a.start[(size_t)min(t + 1, L - 1) * B + frow];
-#else
-        if (tid < RW) stf[tid] = st_next;
-        if (tid < RW && t + 1 < L) st_next = (row0 + tid < B && a.start[(size_t)(t + 1) * B + row0 + tid]) ? 1 : 0;
-#endif
         float4 xn[XPT];
         if (t + 1 < L) load_x(t + 1, xn);
         // the x part of the product (needs nothing from the group)
@@ -287,9 +321,7 @@ __global__ __launch_bounds__(256, 1) void lstm_rows_fwd_kernel(RowsFwd a) {
             const int f = tid + 256 * i;
             *reinterpret_cast<float4 *>(&hsl[f >> 6][4 * (f & 63)]) = hv[i];
         }
-#if VN_ROWS_FLAGS
         if (tid < RW) stf2[(t + 1) & 1][tid] = (t + 1 < L && row0 + tid < B && st_ld) ? 1 : 0;
-#endif
         __syncthreads();
         // ... then the rows that start a sequence at t (all of them at t = 0)
         // take the buffer's stored state x keep: one row per 64 threads
@@ -332,18 +364,10 @@ __global__ __launch_bounds__(256, 1) void lstm_rows_fwd_kernel(RowsFwd a) {
                      f4(k);
             }
             float4 ig, fg, gg, og, cn, hn;
-#define VN_CELL(c)                                 \
-    ig.c = sigm(pre[0].c);                         \
-    fg.c = sigm(pre[1].c);                         \
-    gg.c = tanh_fast(pre[2].c);                        \
-    og.c = sigm(pre[3].c);                         \
-    {                                              \
-        const float fc_ = fg.c * cp.c, ig_ = ig.c * gg.c; \
-        cn.c = fc_ + ig_;                          \
-    }                                              \
-    hn.c = og.c * tanh_fast(cn.c);
-            VN_CELL(x) VN_CELL(y) VN_CELL(z) VN_CELL(w)
-#undef VN_CELL
+            cell_fwd(pre[0].x, pre[1].x, pre[2].x, pre[3].x, cp.x, ig.x, fg.x, gg.x, og.x, cn.x, hn.x);
+            cell_fwd(pre[0].y, pre[1].y, pre[2].y, pre[3].y, cp.y, ig.y, fg.y, gg.y, og.y, cn.y, hn.y);
+            cell_fwd(pre[0].z, pre[1].z, pre[2].z, pre[3].z, cp.z, ig.z, fg.z, gg.z, og.z, cn.z, hn.z);
+            cell_fwd(pre[0].w, pre[1].w, pre[2].w, pre[3].w, cp.w, ig.w, fg.w, gg.w, og.w, cn.w, hn.w);
             cc = cn;
             const size_t so = (((size_t)l * L + t) * B + erow) * H + eu;
             st_sc1(hrs, (uint32_t)(so * 4u), hn);          // the payload first
@@ -357,17 +381,14 @@ __global__ __launch_bounds__(256, 1) void lstm_rows_fwd_kernel(RowsFwd a) {
             *reinterpret_cast<float4 *>(pa + 2 * H) = gg;
             *reinterpret_cast<float4 *>(pa + 3 * H) = og;
         }
-        // h_t published (the payload stores were drained above; the barrier
-        // inside publish orders every wave's drain before the one add)
-        __syncthreads();
-        if (tid == 0) __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        publish_drained(cnt);   // h_t published (the payload store was drained above)
     }
 }
 
 // ---------------------------------------------------------------------------
-// Two blocks per CU (the default).  The same recurrence with HALF the units
-// per block (16: 64 gate columns) on v_mfma_f32_16x16x4_f32, so the grid is
-// 2 x 16 x R/32 = 512 blocks, two resident per CU.  A group (LSTM, row tile)
+// The 16-unit layout.  The same recurrence with HALF the units per block (16:
+// 64 gate columns) on v_mfma_f32_16x16x4_f32, so the grid is 2 x 16 x R/32
+// blocks: 512 at 512 rows, two resident per CU.  A group (LSTM, row tile)
 // is now 16 blocks; the two blocks sharing a CU are different groups (the
 // grid's second half takes the other LSTM of the same row tile), i.e. two
 // independent recurrences, so one's MFMAs run while the other's hand-off is
@@ -421,18 +442,22 @@ __global__ __launch_bounds__(256, 2) void lstm_rows_fwd2_kernel(RowsFwd a) {
     __shared__ __attribute__((aligned(16))) float xs[2][RW][XP];
     __shared__ __attribute__((aligned(16))) float hsl[RW][HP];
     __shared__ __attribute__((aligned(16))) float gts[4][RW][GP];
-#if !VN_ROWS_FLAGS
-    __shared__ uint8_t stf[RW];
-#endif
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);   // this wave's gate
     const int q = lane >> 4, ci = lane & 15;
     int ub, g;
     rows2_map(a.NT, ub, g);
+#if VN_ROWS_DIAG
     if (a.diag && tid == 0) {
         a.diag[2 * blockIdx.x] = __builtin_amdgcn_s_getreg((31 << 11) | 4);        // HW_ID
         a.diag[2 * blockIdx.x + 1] = __builtin_amdgcn_s_getreg((31 << 11) | 20);   // XCC_ID
     }
+#define VN_DMARK(k_)                                                                          \
+    if (a.diag && tid == 0)                                                                   \
+        a.diag[2 * gridDim.x + ((size_t)blockIdx.x * L + t) * 8 + (k_)] = (uint32_t)__builtin_amdgcn_s_memrealtime();
+#else
+#define VN_DMARK(k_)
+#endif
     const int l = g / a.NT, rt = g - l * a.NT;
     const int row0 = rt * RW, u0 = ub * UB2;
     const int B = a.B, L = a.L;
@@ -488,29 +513,17 @@ __global__ __launch_bounds__(256, 2) void lstm_rows_fwd2_kernel(RowsFwd a) {
     }
     __syncthreads();
 
-#define VN_DMARK(k_)                                                                          \
-    if (a.diag && tid == 0)                                                                   \
-        a.diag[2 * gridDim.x + ((size_t)blockIdx.x * L + t) * 8 + (k_)] = (uint32_t)__builtin_amdgcn_s_memrealtime();
     // the tile's sequence-start flags, loaded a step ahead (a load consumed in
     // the same step stalled the x part behind its round trip)
-#if VN_ROWS_FLAGS
     // (double-buffered in LDS as in lstm_rows_fwd_kernel)
     __shared__ uint8_t stf2[2][RW];
     if (tid < RW) stf2[0][tid] = row0 + tid < B ? 1 : 0;
     const int frow = min(row0 + (tid & (RW - 1)), B - 1);
-#else
-    uint8_t st_next = (tid < RW && row0 + tid < B) ? 1 : 0;
-#endif
     for (int t = 0; t < L; ++t) {
         const int xb = t & 1;
         VN_DMARK(0);
-#if VN_ROWS_FLAGS
         const uint8_t *stf = stf2[t & 1];
         const uint8_t st_ld = a.start[(size_t)min(t + 1, L - 1) * B + frow];
-#else
-        if (tid < RW) stf[tid] = st_next;
-        if (tid < RW && t + 1 < L) st_next = (row0 + tid < B && a.start[(size_t)(t + 1) * B + row0 + tid]) ? 1 : 0;
-#endif
         float4 xn[XPT];
         if (t + 1 < L) load_x(t + 1, xn);
         // the x part (needs nothing from the group): rows ci and 16 + ci
@@ -549,9 +562,7 @@ __global__ __launch_bounds__(256, 2) void lstm_rows_fwd2_kernel(RowsFwd a) {
             const int f = tid + 256 * i;
             *reinterpret_cast<float4 *>(&hsl[f >> 6][4 * (f & 63)]) = hv[i];
         }
-#if VN_ROWS_FLAGS
         if (tid < RW) stf2[(t + 1) & 1][tid] = (t + 1 < L && row0 + tid < B && st_ld) ? 1 : 0;
-#endif
         __syncthreads();
         VN_DMARK(3);
 #pragma unroll
@@ -603,18 +614,8 @@ __global__ __launch_bounds__(256, 2) void lstm_rows_fwd2_kernel(RowsFwd a) {
                      f2(k);
             }
             float2 ig, fg, gg, og, cn, hn;
-#define VN_CELL2(c)                                       \
-    ig.c = sigm(pre[0].c);                                \
-    fg.c = sigm(pre[1].c);                                \
-    gg.c = tanh_fast(pre[2].c);                           \
-    og.c = sigm(pre[3].c);                                \
-    {                                                     \
-        const float fc_ = fg.c * cp.c, ig_ = ig.c * gg.c; \
-        cn.c = fc_ + ig_;                                 \
-    }                                                     \
-    hn.c = og.c * tanh_fast(cn.c);
-            VN_CELL2(x) VN_CELL2(y)
-#undef VN_CELL2
+            cell_fwd(pre[0].x, pre[1].x, pre[2].x, pre[3].x, cp.x, ig.x, fg.x, gg.x, og.x, cn.x, hn.x);
+            cell_fwd(pre[0].y, pre[1].y, pre[2].y, pre[3].y, cp.y, ig.y, fg.y, gg.y, og.y, cn.y, hn.y);
             cc = cn;
             const size_t so = (((size_t)l * L + t) * B + erow) * H + eu;
             st_sc1_b64(hrs, (uint32_t)(so * 4u), hn);      // the payload first
@@ -629,8 +630,7 @@ __global__ __launch_bounds__(256, 2) void lstm_rows_fwd2_kernel(RowsFwd a) {
             *reinterpret_cast<float2 *>(pa + 3 * H) = og;
         }
         VN_DMARK(5);
-        __syncthreads();
-        if (tid == 0) __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        publish_drained(cnt);
         if (a.prio) __builtin_amdgcn_s_setprio(0);
         VN_DMARK(6);
     }
@@ -655,224 +655,14 @@ struct RowsBwd {
     int prio;
 };
 
-// Backward.  Besides the recurrence, each block accumulates the weight
-// gradients of its 128 gate rows over all steps and its 32 rows: dW_hh +=
-// dG_t^T h_{t-1}, dW_ih += dG_t^T x_t, db += sum dG_t, on the matrix cores
-// with the accumulators resident (wave w: gate w's 32 rows, 8 + 3 tiles of
-// 32 x 32).  Those products do not feed the recurrence, so they are issued
-// after the step's partial is published and run while the group's next
-// hand-off is in flight.  Per-row-tile partials are summed (fixed order) by
-// rows_wsum_kernel.
-template <int D, int H>
-__global__ __launch_bounds__(256, 1) void lstm_rows_bwd_kernel(RowsBwd a) {
-    constexpr int GC = 4 * UBK;   // this block's gate columns (K of the partial product)
-    constexpr int NCK = GC / 8;   // 16 chunks
-    constexpr int DP = GC + 4, PP = H + 4, XP = 96;   // xs padded to 3 tiles of 32 (zeros past D)
-    constexpr int NXT = (D + 31) / 32;                 // dW_ih column tiles
-    static_assert(H == NUB * UBK && D <= XP && D % 4 == 0 && H == 256 && D / 4 <= 64, "shape: a row per wave load");
-    __shared__ __attribute__((aligned(16))) float dgs[RW][DP];
-    __shared__ __attribute__((aligned(16))) float pst[RW][PP];
-    __shared__ __attribute__((aligned(16))) float hsl[RW][PP];
-    __shared__ __attribute__((aligned(16))) float xsl[RW][XP];
-    __shared__ uint8_t stf[RW];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);   // output units 64 wv .. + 63; dW gate wv
-    const int hh = lane >> 5, cl = lane & 31;
-    const int G = 2 * a.NT;
-    const int ub = (int)blockIdx.x / G, g = (int)blockIdx.x - ub * G;
-    const int l = g / a.NT, rt = g - l * a.NT;
-    const int row0 = rt * RW, u0 = ub * UBK;
-    const int B = a.B, L = a.L;
-
-    // resident W_hh slice: B operand [k = gate * 32 + unit32][n = 64 wv + 32 j + cl],
-    // k = 8 ch + 4 hh + jj
-    float4 wb[2][NCK];
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int ch = 0; ch < NCK; ++ch) {
-            float v[4];
-#pragma unroll
-            for (int jj = 0; jj < 4; ++jj) {
-                const int k = 8 * ch + 4 * hh + jj;
-                const int grow = (k >> 5) * H + u0 + (k & 31);
-                v[jj] = a.w_hh[((size_t)l * 4 * H + grow) * H + 64 * wv + 32 * j + cl];
-            }
-            wb[j][ch] = make_float4(v[0], v[1], v[2], v[3]);
-        }
-    const int er = tid >> 3, eq = tid & 7;
-    const int erow = row0 + er;
-    const bool elive = erow < B;
-    const int eu = u0 + 4 * eq;
-    float4 dc = f4(0.0f);
-    float4 dbs[4] = {f4(0.0f), f4(0.0f), f4(0.0f), f4(0.0f)};
-    f32x16_t wacc[8], xacc[NXT];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) wacc[j] = zero16();
-#pragma unroll
-    for (int j = 0; j < NXT; ++j) xacc[j] = zero16();
-    const size_t slot_f = (size_t)2 * a.NT * NUB * RW * H;     // floats per slot
-    const __amdgpu_buffer_rsrc_t prs =
-        __builtin_amdgcn_make_buffer_rsrc(a.part, 0, (int)(2 * slot_f * 4), 0x00020000);
-    uint32_t *cnt = a.cnt + (size_t)g * CSTRIDE;
-    auto pofs = [&](int slot, int ubb, int row, int unit) -> uint32_t {   // byte offset in part
-        return (uint32_t)(((size_t)slot * slot_f + ((((size_t)l * a.NT + rt) * NUB + ubb) * RW + row) * H + unit) * 4u);
-    };
-    // zero the padding columns of xs once (never written by the staging)
-#pragma unroll
-    for (int i = tid; i < RW * (XP - D); i += 256) xsl[i / (XP - D)][D + i % (XP - D)] = 0.0f;
-
-    for (int s = 0; s < L; ++s) {
-        const int t = L - 1 - s;
-        // the step's sequence-start flag, loaded ahead of the hand-off wait
-        const bool st_ld = !elive || t == 0 || a.start[(size_t)t * B + erow];
-        // the step's h_{t-1} and x_t rows (the weight gradients' B operands; rows
-        // past B clamped: their dG is zero), copied global -> LDS directly (no
-        // registers: the kernel sits at the VGPR cap, and register staging made
-        // the compiler serialise the loads), issued before the hand-off wait so
-        // they land while it is awaited (the previous step's weight-gradient
-        // reads of hsl / xsl ended at its closing barrier).  One wave
-        // instruction = one row.
-#pragma unroll
-        for (int i = 0; i < RW / 4; ++i) {
-            const int rr = (RW / 4) * wv + i;
-            const int row = min(row0 + rr, B - 1);
-            __builtin_amdgcn_global_load_lds(
-                (const __attribute__((address_space(1))) void *)(a.hprev + (((size_t)l * L + t) * B + row) * H + 4 * lane),
-                (__attribute__((address_space(3))) void *)&hsl[rr][0], 16, 0, 0);
-            if (lane < D / 4)
-                __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) void *)(a.x + ((size_t)t * B + row) * D + 4 * lane),
-                    (__attribute__((address_space(3))) void *)&xsl[rr][0], 16, 0, 0);
-        }
-        if (s > 0) {
-            if (tid == 0) wait_ge(cnt, (uint32_t)(NUB * s), a.err);
-            __syncthreads();
-        }
-        float4 dG4[4] = {f4(0.0f), f4(0.0f), f4(0.0f), f4(0.0f)};
-        bool st = true;
-        if (elive) {
-            st = st_ld;
-            float4 dhr = f4(0.0f);
-            if (s > 0) {
-                // the 8 partials of step t+1 (sc1 loads), summed in unit-block order
-#pragma unroll
-                for (int k = 0; k < NUB; ++k) dhr = dhr + ld_sc1(prs, pofs((t + 1) & 1, k, er, eu));
-            }
-            const size_t so = (((size_t)l * L + t) * B + erow) * H + eu;
-            const float4 dh = *reinterpret_cast<const float4 *>(a.dh_out + so) + dhr;
-            const float *pa = a.act + (((size_t)l * L + t) * B + erow) * 4 * H + eu;
-            const float4 ig = *reinterpret_cast<const float4 *>(pa), fg = *reinterpret_cast<const float4 *>(pa + H);
-            const float4 gg = *reinterpret_cast<const float4 *>(pa + 2 * H);
-            const float4 og = *reinterpret_cast<const float4 *>(pa + 3 * H);
-            const float4 cp = *reinterpret_cast<const float4 *>(a.cprev + so);
-            const float4 cn = *reinterpret_cast<const float4 *>(a.cnew + so);
-#define VN_CELLB(c)                                                   \
-    {                                                                 \
-        const float tc = tanh_fast(cn.c);                                 \
-        const float dtc = dh.c * og.c;                                \
-        const float dcc = dc.c + dtc * (1.0f - tc * tc);              \
-        dG4[0].c = dcc * gg.c * (ig.c * (1.0f - ig.c));               \
-        dG4[1].c = dcc * cp.c * (fg.c * (1.0f - fg.c));               \
-        dG4[2].c = dcc * ig.c * (1.0f - gg.c * gg.c);                 \
-        dG4[3].c = dh.c * tc * (og.c * (1.0f - og.c));                \
-        dc.c = dcc * fg.c;                                            \
-    }
-            VN_CELLB(x) VN_CELLB(y) VN_CELLB(z) VN_CELLB(w)
-#undef VN_CELLB
-            if (st) dc = f4(0.0f);   // c_{t-1} of this row came from the buffer
-            if (a.dG) {
-                float *pg = a.dG + (((size_t)l * L + t) * B + erow) * 4 * H + eu;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) *reinterpret_cast<float4 *>(pg + q * H) = dG4[q];
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) dbs[q] = dbs[q] + dG4[q];
-        }
-        // dG (the partial product's and the weight gradients' A operand) and
-        // the sequence-start flags to LDS
-#pragma unroll
-        for (int q = 0; q < 4; ++q) *reinterpret_cast<float4 *>(&dgs[er][q * UBK + 4 * eq]) = dG4[q];
-        if (eq == 0) stf[er] = st ? 1 : 0;
-        __syncthreads();
-        if (t > 0) {
-            f32x16_t acc0 = zero16(), acc1 = zero16();
-#pragma unroll
-            for (int ch = 0; ch < NCK; ++ch) {
-                const float4 av = *reinterpret_cast<const float4 *>(&dgs[cl][8 * ch + 4 * hh]);
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, wb[0][ch].x, acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.x, wb[1][ch].x, acc1, 0, 0, 0);
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, wb[0][ch].y, acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.y, wb[1][ch].y, acc1, 0, 0, 0);
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, wb[0][ch].z, acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.z, wb[1][ch].z, acc1, 0, 0, 0);
-                acc0 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, wb[0][ch].w, acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(av.w, wb[1][ch].w, acc1, 0, 0, 0);
-            }
-            // rows whose step t starts a sequence pass no gradient back
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const int r = 8 * (v >> 2) + 4 * hh + (v & 3);
-                const bool cut = stf[r] != 0;
-                pst[r][64 * wv + cl] = cut ? 0.0f : acc0[v];
-                pst[r][64 * wv + 32 + cl] = cut ? 0.0f : acc1[v];
-            }
-            __syncthreads();
-            // the partial [RW][H] of this block: 16-B sc1 stores, then publish
-#pragma unroll
-            for (int i = 0; i < 8; ++i) {
-                const int f = tid + 256 * i;
-                const int rr = f >> 6, c4 = f & 63;
-                st_sc1(prs, pofs(t & 1, ub, rr, 4 * c4), *reinterpret_cast<const float4 *>(&pst[rr][4 * c4]));
-            }
-            publish(cnt);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        // weight gradients of gate wv's 32 rows (while the next hand-off is in flight):
-        // A = dG^T [gate unit][row], B = h_{t-1} / x_t [row][col], K = the 32 rows
-#pragma unroll
-        for (int ks = 0; ks < RW / 2; ++ks) {
-            const int r = 2 * ks + hh;
-            const float av = dgs[r][wv * UBK + cl];
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                wacc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, hsl[r][32 * j + cl], wacc[j], 0, 0, 0);
-#pragma unroll
-            for (int j = 0; j < NXT; ++j)
-                xacc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, xsl[r][32 * j + cl], xacc[j], 0, 0, 0);
-        }
-        // every wave done reading hsl / xsl before the next step's copies into them
-        __syncthreads();
-        if (t == 0) break;
-    }
-    // per-row-tile weight-gradient partials: register v of a tile = gate row
-    // 8 (v / 4) + 4 hh + v % 4 of gate wv's 32, column 32 j + cl
-    float *wp = a.wpart + (((size_t)rt * 2 + l) * 4 * H) * (H + D);
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-        const int grow = wv * H + u0 + 8 * (v >> 2) + 4 * hh + (v & 3);
-        float *prow = wp + (size_t)grow * (H + D);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) prow[32 * j + cl] = wacc[j][v];
-#pragma unroll
-        for (int j = 0; j < NXT; ++j)
-            if (32 * j + cl < D) prow[H + 32 * j + cl] = xacc[j][v];
-    }
-    // db: the 32 rows' sums (threads of one eq hold a row each), reduced through LDS
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 4; ++q) *reinterpret_cast<float4 *>(&pst[er][q * UBK + 4 * eq]) = dbs[q];
-    __syncthreads();
-    if (tid < 4 * UBK) {
-        float sum = 0.0f;
-        for (int r = 0; r < RW; ++r) sum += pst[r][tid];
-        a.bpart[((size_t)rt * 2 + l) * 4 * H + (tid >> 5) * H + u0 + (tid & 31)] = sum;
-    }
-}
-
-// Backward, two blocks per CU (block = 16 units: 64 gate columns; the grid
-// mapping of the forward).  The partial dh_{t-1} [32 rows][256 units] of a
+// Backward (block = 16 units: 64 gate columns; the grid mapping of the
+// 16-unit forward).  Besides the recurrence, each block accumulates the weight
+// gradients of its 64 gate rows over all steps and its 32 rows: dW_hh +=
+// dG_t^T h_{t-1}, dW_ih += dG_t^T x_t, db += sum dG_t, on the matrix cores with
+// the accumulators resident.  Those products do not feed the recurrence, so
+// they are issued after the step's partial is published and run while the
+// group's next hand-off is in flight.  Per-row-tile partials are summed (fixed
+// order) by rows_wsum_kernel.  The partial dh_{t-1} [32 rows][256 units] of a
 // block is dG_t[:, its 64 gate columns] @ W_hh[those rows] on 16x16x4 tiles
 // (wave w: units 64 w .. + 63, W_hh slice resident in 64 registers), staged
 // through LDS 16 rows at a time; the weight gradients of gate wv's 16 rows
@@ -951,7 +741,6 @@ __global__ __launch_bounds__(256, 2) void lstm_rows_bwd2_kernel(RowsBwd a) {
                     (const __attribute__((address_space(1))) void *)(a.x + ((size_t)t * B + row) * D + 4 * lane),
                     (__attribute__((address_space(3))) void *)&xsl[rr][0], 16, 0, 0);
         }
-#if VN_ROWS_PRELOAD
         // the step's own cell operands (dh_out, the 4 gates, c_{t-1}, c_t) need
         // nothing from the group: global -> LDS before the hand-off wait, each
         // wave the 8 rows its cell lanes read (so no barrier is needed, only the
@@ -970,7 +759,6 @@ __global__ __launch_bounds__(256, 2) void lstm_rows_bwd2_kernel(RowsBwd a) {
                 __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(src + u0 + 4 * (lane & 3)),
                                                  (__attribute__((address_space(3))) void *)(cops + 256 * k), 16, 0, 0);
         }
-#endif
         if (a.prio) __builtin_amdgcn_s_setprio(2);   // the hand-off path up to the publish
         if (s > 0) {
             if (tid == 0) wait_ge(cnt, (uint32_t)(NUB2 * s), a.err);
@@ -985,35 +773,13 @@ __global__ __launch_bounds__(256, 2) void lstm_rows_bwd2_kernel(RowsBwd a) {
 #pragma unroll
                 for (int k = 0; k < NUB2; ++k) dhr = dhr + ld_sc1_b64(prs, pofs((t + 1) & 1, k, er, eu));
             }
-#if VN_ROWS_PRELOAD
             auto cop = [&](int op) {   // this lane's 2 units of operand op
                 return *reinterpret_cast<const float2 *>(cops + 128 * op + 16 * (lane >> 3) + 2 * eq);
             };
             const float2 dh = cop(0) + dhr;
             const float2 ig = cop(1), fg = cop(2), gg = cop(3), og = cop(4), cp = cop(5), cn = cop(6);
-#else
-            const size_t so = (((size_t)l * L + t) * B + erow) * H + eu;
-            const float2 dh = *reinterpret_cast<const float2 *>(a.dh_out + so) + dhr;
-            const float *pa = a.act + (((size_t)l * L + t) * B + erow) * 4 * H + eu;
-            const float2 ig = *reinterpret_cast<const float2 *>(pa), fg = *reinterpret_cast<const float2 *>(pa + H);
-            const float2 gg = *reinterpret_cast<const float2 *>(pa + 2 * H);
-            const float2 og = *reinterpret_cast<const float2 *>(pa + 3 * H);
-            const float2 cp = *reinterpret_cast<const float2 *>(a.cprev + so);
-            const float2 cn = *reinterpret_cast<const float2 *>(a.cnew + so);
-#endif
-#define VN_CELLB2(c)                                                  \
-    {                                                                 \
-        const float tc = tanh_fast(cn.c);                             \
-        const float dtc = dh.c * og.c;                                \
-        const float dcc = dc.c + dtc * (1.0f - tc * tc);              \
-        dG2[0].c = dcc * gg.c * (ig.c * (1.0f - ig.c));               \
-        dG2[1].c = dcc * cp.c * (fg.c * (1.0f - fg.c));               \
-        dG2[2].c = dcc * ig.c * (1.0f - gg.c * gg.c);                 \
-        dG2[3].c = dh.c * tc * (og.c * (1.0f - og.c));                \
-        dc.c = dcc * fg.c;                                            \
-    }
-            VN_CELLB2(x) VN_CELLB2(y)
-#undef VN_CELLB2
+            cell_bwd(dh.x, ig.x, fg.x, gg.x, og.x, cp.x, cn.x, dc.x, dG2[0].x, dG2[1].x, dG2[2].x, dG2[3].x);
+            cell_bwd(dh.y, ig.y, fg.y, gg.y, og.y, cp.y, cn.y, dc.y, dG2[0].y, dG2[1].y, dG2[2].y, dG2[3].y);
             if (st) dc = f2(0.0f);
             if (a.dG) {
                 float *pg = a.dG + (((size_t)l * L + t) * B + erow) * 4 * H + eu;
@@ -1151,21 +917,22 @@ __global__ void rows_bsum_kernel(const float *__restrict__ part, int nt, int64_t
 
 int rows_supported(int D, int H) { return D == 80 && H == 256; }
 
-// which layout a direction runs: the 16-unit blocks (v2) whenever their grid
-// is at most one block per CU (measured 6.8 vs 9.4 us per forward step at 256
-// rows); at two per CU the two blocks of a CU run their steps in phase (their
-// matrix work shares the SIMDs, an offset start decays to alignment within ~8
-// steps), so the forward keeps the 32-unit blocks there (9.4 vs 9.9 us) and the
-// backward the 16-unit ones (14.8 vs 15.4 us).  VN_OPT_ROWS_LAYOUT 1 / 2 force
-// one layout (A/B and tests; read per call).
-bool rows_v2(int NT, bool fwd) {
+// which layout the forward runs (the backward has one, the 16-unit blocks:
+// 14.8 vs 15.4 us per step at 512 rows, 10.5 vs 14.9 at 256): the 16-unit
+// blocks (v2) whenever their grid is at most one block per CU (measured 6.8 vs
+// 9.4 us per forward step at 256 rows); at two per CU the two blocks of a CU
+// run their steps in phase (their matrix work shares the SIMDs, an offset
+// start decays to alignment within ~8 steps), so the forward keeps the 32-unit
+// blocks there (9.4 vs 9.9 us).  VN_OPT_ROWS_LAYOUT 1 / 2 force one forward
+// layout (A/B and tests; read per call).
+bool rows_fwd_v2(int NT) {
     const int32_t layout = vn_detail::option(VN_OPT_ROWS_LAYOUT);
     if (layout) return layout == 2;
     int dev = 0, ncu = 0;
     if (hipGetDevice(&dev) != hipSuccess ||
         hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
         return false;
-    return 2 * NUB2 * NT <= ncu || !fwd;
+    return 2 * NUB2 * NT <= ncu;
 }
 
 // the 16-unit kernels raise the issue priority on the hand-off path (wait,
@@ -1174,27 +941,26 @@ bool rows_v2(int NT, bool fwd) {
 // (backward 15.1 -> 14.2 us per step at 512 rows).  VN_OPT_ROWS_PRIO 0: off.
 int rows_prio() { return vn_detail::option(VN_OPT_ROWS_PRIO); }
 
-uint32_t *g_rows_diag = nullptr;   // vn_lstm_rows_set_diag (diagnostics)
+#if VN_ROWS_DIAG
+uint32_t *g_rows_diag = nullptr;   // vn_lstm_rows_set_diag
+#endif
 
-int rows_grid_ok(int B, int NT, bool v2, int *grid) {
-    *grid = 2 * (v2 ? NUB2 : NUB) * NT;
+// every block of a launch must be resident at once (a block spins on its
+// group's counter): the forward's grid against the kernel it will launch, the
+// backward's against its one kernel
+int rows_grid_ok(int B, int NT, bool fwd_v2, int *grid_fwd, int *grid_bwd) {
+    *grid_fwd = 2 * (fwd_v2 ? NUB2 : NUB) * NT;
+    *grid_bwd = 2 * NUB2 * NT;
     if (B < 1 || NT < 1 || B > NT * RW) return 0;
     int dev = 0, ncu = 0, per_fwd = 0, per_bwd = 0;
     if (hipGetDevice(&dev) != hipSuccess) return 0;
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
-    if (v2) {
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_fwd, lstm_rows_fwd2_kernel<80, 256>, 256, 0) != hipSuccess)
-            return 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_bwd, lstm_rows_bwd2_kernel<80, 256>, 256, 0) != hipSuccess)
-            return 0;
-    } else {
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_fwd, lstm_rows_fwd_kernel<80, 256>, 256, 0) != hipSuccess)
-            return 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_bwd, lstm_rows_bwd_kernel<80, 256>, 256, 0) != hipSuccess)
-            return 0;
-    }
-    const int cap = ncu * (per_fwd < per_bwd ? per_fwd : per_bwd);
-    return *grid <= cap;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_bwd, lstm_rows_bwd2_kernel<80, 256>, 256, 0) != hipSuccess)
+        return 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_fwd, fwd_v2 ? lstm_rows_fwd2_kernel<80, 256>
+                                                                      : lstm_rows_fwd_kernel<80, 256>, 256, 0) != hipSuccess)
+        return 0;
+    return *grid_fwd <= ncu * per_fwd && *grid_bwd <= ncu * per_bwd;
 }
 
 }  // namespace
@@ -1203,18 +969,17 @@ extern "C" {
 
 int vn_lstm_rows_supported(int32_t D, int32_t H, int32_t B) {
     if (!rows_supported(D, H)) return 0;
-    int grid = 0;
+    int grid_fwd = 0, grid_bwd = 0;
     const int NT = (B + RW - 1) / RW;
-    return rows_grid_ok(B, NT, rows_v2(NT, true), &grid) && rows_grid_ok(B, NT, rows_v2(NT, false), &grid);
+    return rows_grid_ok(B, NT, rows_fwd_v2(NT), &grid_fwd, &grid_bwd);
 }
 
-// diagnostics: the forward (two-per-CU layout) records each block's HW_ID /
-// XCC_ID in diag[2 b], diag[2 b + 1] and the 100-MHz clock at 7 points of
-// its step t in diag[2 grid + (b L + t) 8 + k]; NULL turns it off.  Not in voxnav.h.
-int vn_lstm_rows_set_diag(void *diag) {
+#if VN_ROWS_DIAG
+int vn_lstm_rows_set_diag(void *diag) {   // not in voxnav.h
     g_rows_diag = (uint32_t *)diag;
     return VN_OK;
 }
+#endif
 
 int vn_lstm_rows_part_floats(int32_t B, int64_t *floats) {
     if (!floats || B < 1) return fail(VN_ERR_INVALID, "bad argument");
@@ -1234,15 +999,18 @@ int vn_lstm_rows_fwd(const float *x, int32_t D, const float *w_ih, const float *
     if (!rows_supported(D, H)) return fail(VN_ERR_INVALID, "row-layout LSTM: D 80 and H 256 only (got %d, %d)", D, H);
     if (L < 1) return fail(VN_ERR_INVALID, "L < 1");
     const int NT = (B + RW - 1) / RW;
-    const bool v2 = rows_v2(NT, true);
-    int grid = 0;
-    if (!rows_grid_ok(B, NT, v2, &grid))
+    const bool v2 = rows_fwd_v2(NT);
+    int grid = 0, grid_bwd = 0;
+    if (!rows_grid_ok(B, NT, v2, &grid, &grid_bwd))
         return fail(VN_ERR_INVALID, "row-layout LSTM: %d blocks are not co-resident (B = %d)", grid, B);
     if ((size_t)2 * L * B * H * 4 >= (1ull << 31)) return fail(VN_ERR_INVALID, "row-layout LSTM: hout over 2 GB");
     const hipStream_t st = (hipStream_t)stream;
     VN_HIP(hipMemsetAsync(cnt, 0, (size_t)2 * NT * CSTRIDE * sizeof(uint32_t), st));
     RowsFwd a{x, w_ih, w_hh, bias, h_store, c_store, env, start, keep, hout, hprev, cprev, cnew, act, cnt, err,
-              n_env, L, B, NT, rows_prio(), g_rows_diag};
+              n_env, L, B, NT, rows_prio()};
+#if VN_ROWS_DIAG
+    a.diag = g_rows_diag;
+#endif
     if (v2) hipLaunchKernelGGL((lstm_rows_fwd2_kernel<80, 256>), dim3((unsigned)grid), dim3(256), 0, st, a);
     else hipLaunchKernelGGL((lstm_rows_fwd_kernel<80, 256>), dim3((unsigned)grid), dim3(256), 0, st, a);
     VN_HIP(hipGetLastError());
@@ -1259,19 +1027,17 @@ int vn_lstm_rows_bwd(const float *dh_out, const float *w_hh, const float *act, c
     if (!rows_supported(80, H)) return fail(VN_ERR_INVALID, "row-layout LSTM: H 256 only (got %d)", H);
     if (L < 1) return fail(VN_ERR_INVALID, "L < 1");
     const int NT = (B + RW - 1) / RW;
-    const bool v2 = rows_v2(NT, false);
-    int grid = 0;
-    if (!rows_grid_ok(B, NT, v2, &grid))
+    int grid_fwd = 0, grid = 0;
+    if (!rows_grid_ok(B, NT, rows_fwd_v2(NT), &grid_fwd, &grid))
         return fail(VN_ERR_INVALID, "row-layout LSTM: %d blocks are not co-resident (B = %d)", grid, B);
     const hipStream_t st = (hipStream_t)stream;
     constexpr int D = 80;
-    const size_t slot_f = (size_t)2 * NT * (v2 ? NUB2 : NUB) * RW * H;
+    const size_t slot_f = (size_t)2 * NT * NUB2 * RW * H;
     float *wpart = part + 2 * slot_f;
     float *bpart = wpart + (size_t)NT * 2 * 4 * H * (H + D);
     VN_HIP(hipMemsetAsync(cnt, 0, (size_t)2 * NT * CSTRIDE * sizeof(uint32_t), st));
     RowsBwd a{dh_out, w_hh, act, cprev, cnew, hprev, x, start, dG, part, wpart, bpart, cnt, err, L, B, NT, rows_prio()};
-    if (v2) hipLaunchKernelGGL((lstm_rows_bwd2_kernel<80, 256>), dim3((unsigned)grid), dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((lstm_rows_bwd_kernel<80, 256>), dim3((unsigned)grid), dim3(256), 0, st, a);
+    hipLaunchKernelGGL((lstm_rows_bwd2_kernel<80, 256>), dim3((unsigned)grid), dim3(256), 0, st, a);
     const int64_t pw = (int64_t)2 * 4 * H * (H + D), pb = (int64_t)2 * 4 * H;
     hipLaunchKernelGGL(rows_wsum_kernel, dim3((unsigned)((pw + 255) / 256)), dim3(256), 0, st, wpart, NT, 4 * H, H, D,
                        dw_hh, dw_ih);

@@ -555,8 +555,9 @@ int vn_reward_normalize(float *rewards, int32_t t0, int32_t t1, int32_t N, doubl
  * out-of-range value.  No reference counterpart.
  */
 enum {
-    VN_OPT_ROWS_LAYOUT = 0,  /* vn_lstm_rows_*: 0 auto (by grid size and direction),
-                                1 blocks of 32 units, 2 blocks of 16 units; default 0 */
+    VN_OPT_ROWS_LAYOUT = 0,  /* vn_lstm_rows_fwd's layout (the backward has one): 0 auto
+                                (by grid size against the CU count), 1 blocks of 32
+                                units, 2 blocks of 16 units; default 0               */
     VN_OPT_ROWS_PRIO = 1,    /* 16-unit row kernels raise the issue priority on the
                                 hand-off path: 0 / 1; default 1                      */
     VN_OPT_GEMM_DL = 2,      /* vn_gemm_f32_*: the direct-load kernel where operands

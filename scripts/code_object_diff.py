@@ -79,7 +79,9 @@ def functions(elf: bytes):
             cur = out.setdefault(head.group(1), []) if head.group(1) in size else None
             continue
         ins = ln.split("//")[0].strip()
-        if cur is None or not ins:
+        # "...": objdump's elision of the zero padding up to the next function's
+        # alignment, outside the symbol's size; the unit's last function has none
+        if cur is None or not ins or ins == "...":
             continue
         # s_getpc_b64, then s_add_u32 / s_addc_u32 with the literal
         pc = 2 if ins.startswith("s_getpc_b64") else pc - 1

@@ -1,13 +1,21 @@
 #!/usr/bin/env python3
 """Placement and per-step clocks of the two-per-CU row forward
-(vn_lstm_rows_set_diag, diagnostics): which blocks share a CU, which groups
-they belong to, and each group's step durations."""
+(vn_lstm_rows_set_diag): which blocks share a CU, which groups they belong to,
+and each group's step durations.
+
+The records exist only in a diagnostics build with VN_ROWS_DIAG, passed with --lib:
+
+  python scripts/build_variants.py rowsdiag:VN_ROWS_DIAG=1
+  python scripts/rows_diag.py --lib 3d-navigation-reinforcement-learning_amd/voxnav/_lib/variants/libvoxnav_rowsdiag.so
+"""
+import argparse
 import ctypes as C
 import sys
 from collections import defaultdict
 from pathlib import Path
 
-sys.path.insert(0, str(Path(__file__).resolve().parents[1] / "3d-navigation-reinforcement-learning_amd"))
+REPO = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(REPO / "3d-navigation-reinforcement-learning_amd"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 from types import SimpleNamespace  # noqa: E402
@@ -106,6 +114,13 @@ def run(B, mp, L=128):
 
 
 if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--lib", required=True, help="a diagnostics build of the library with VN_ROWS_DIAG=1")
+    a = ap.parse_args()
+    _native.use_library(a.lib if a.lib.startswith("/") else REPO / a.lib)
+    if not hasattr(_native.load(), "vn_lstm_rows_set_diag"):
+        sys.exit(f"{a.lib} has no vn_lstm_rows_set_diag: the row forward's records exist only in a diagnostics "
+                 "build (python scripts/build_variants.py rowsdiag:VN_ROWS_DIAG=1)")
     with _native.option("rows_layout", 2):
         for B in (256, 512):
             run(B, 0)

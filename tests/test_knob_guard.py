@@ -16,7 +16,7 @@ DIRECTIVE = re.compile(r"^\s*#\s*(if|ifdef|ifndef|elif)\b(.*)$")
 # folded to their defaults, the other branch deleted ("Knob retirement")
 RETIRED = ["VN_PHILOX16", "VN_REWARD_STRIPE", "VN_PREMOVE", "VN_STAGE_OBS", "VN_STOOD", "VN_STOOD_PART",
            "VN_DM_CODES", "VN_WREC", "VN_DPP", "VN_ROW_WB", "VN_TAB_SWZ", "VN_OBS_STORE", "VN_SETPRIO",
-           "VN_SETPRIO_FLUSH", "VN_LDS_BARRIER"]
+           "VN_SETPRIO_FLUSH", "VN_LDS_BARRIER", "VN_ROWS_RAWBAR", "VN_ROWS_PRELOAD", "VN_ROWS_FLAGS"]
 
 
 def logical_lines(path):

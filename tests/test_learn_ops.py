@@ -162,9 +162,10 @@ def test_dual_lstm_rows_matches_float64(L, B, N, p_start, layout):
     edge shapes: one step of one row, two steps of a 33-row batch (one full
     tile and a 1-row tile), and a batch where every row starts a sequence at
     every step (no state crosses a step: only the stored states).
-    Both layouts, forced: 16 unit blocks of 16 units (option rows_layout 2; two
-    blocks per CU at 512 rows) and 8 of 32 (rows_layout 1), and the
-    default pick per direction."""
+    Both forward layouts, forced: 16 unit blocks of 16 units (option
+    rows_layout 2; two blocks per CU at 512 rows) and 8 of 32 (rows_layout 1),
+    and the default pick by grid size; the backward has one layout (16 units)
+    and runs behind each."""
     from voxnav import _native
     with _native.option("rows_layout", {"auto": 0, "units32": 1, "units16": 2}[layout]):
         _dual_lstm_rows_vs_float64(L, B, N, p_start)
@@ -207,10 +208,11 @@ def _dual_lstm_rows_vs_float64(L, B, N, p_start):
 @pytest.mark.parametrize("layout", ["auto", "units16", "units32"])
 @pytest.mark.parametrize("L,B,N,p_start", [(9, 37, 40, 0.2), (2, 33, 8, 0.5)])
 def test_dual_lstm_rows_input_gradient_matches_float64(L, B, N, p_start, layout):
-    """The row-layout backward with an input that needs a gradient (dG is
-    only allocated and written then): x.grad and the eight parameter
-    gradients against float64 autograd, and the parameter gradients
-    bit-identical to a run whose x needs none (the learner's own case)."""
+    """The row-layout backward (one layout, behind each forward layout) with an
+    input that needs a gradient (dG is only allocated and written then): x.grad
+    and the eight parameter gradients against float64 autograd, and the
+    parameter gradients bit-identical to a run whose x needs none (the
+    learner's own case)."""
     from types import SimpleNamespace
     from voxnav import _native, lstm_seq
     dev = "cuda:0"
@@ -250,6 +252,23 @@ def test_dual_lstm_rows_input_gradient_matches_float64(L, B, N, p_start, layout)
     _close(dx, x64.grad, rel=1e-4)
     for g, p in zip(got, params):
         _close(g, p.grad, rel=1e-4)
+
+
+@pytest.mark.parametrize("layout", [0, 1, 2])
+def test_rows_supported_up_to_the_co_residency_bound(layout):
+    """Every block of a row-layout launch must be resident at once: 16 blocks
+    per 32-row tile at one per CU (the 32-unit forward) or 32 at two per CU
+    (the 16-unit kernels), so under every rows_layout the kernels take
+    B = 32 * (ncu // 16) rows and refuse one row more.  Launches nothing."""
+    from types import SimpleNamespace
+    from voxnav import _native, lstm_seq
+    D, H = 80, 256
+    pol = SimpleNamespace(lstm_actor=torch.nn.LSTM(D, H), lstm_critic=torch.nn.LSTM(D, H))
+    ncu = torch.cuda.get_device_properties(0).multi_processor_count
+    B = 32 * (ncu // 16)
+    with _native.option("rows_layout", layout):
+        assert lstm_seq.rows_supported(pol, D, B)
+        assert not lstm_seq.rows_supported(pol, D, B + 1)
 
 
 @pytest.mark.parametrize("M,F,A,gather,norm", [(65536, 128, 6, True, True), (77, 64, 3, False, True),
