@@ -1,7 +1,8 @@
 // head_loss.h -- the fused "head loss" of the learner, once: the skeleton that
 // vn_ppo_loss (voxnav_ppo_loss.hip), vn_bc_loss / vn_bc_loss_set
-// (voxnav_bc_loss.hip) and vn_ppo_bc_loss / vn_ppo_bc_loss_set
-// (voxnav_ppo_bc_loss.hip) share; their file headers state the formulas.  Common
+// (voxnav_bc_loss.hip), vn_ppo_bc_loss / vn_ppo_bc_loss_set
+// (voxnav_ppo_bc_loss.hip) and vn_ppo_loss_masked (voxnav_masked_loss.hip)
+// share; their file headers state the formulas.  Common
 // to them, with lp = log_softmax(z), p = exp(lp), H the entropy:
 //   dz_j = (the objective's policy term)_j + (ent_coef / M) p_j (lp_j + H)
 //   dv   = vf_coef 2 (v - ret) / M
@@ -24,6 +25,13 @@
 //   dz(s, f, a)       the policy term of dz_a
 //   stats(s, f, st)   its logged sums
 //   finish(v, M, ent_coef, vf_coef, stats)   sums -> stats[6] (reduce kernel)
+// and, optionally, a compile-time trait: an objective that declares
+//   static constexpr bool kAllowed = true;   allowed(s, A) -> bits of the sample's
+//                     allowed actions, a non-empty subset of bits 0 .. A-1
+// has the softmax, entropy and argmax run over that set only (PpoClipMasked in
+// voxnav_masked_loss.hip: lp_j = z_j - logsumexp_{k in S} z_k, p_j = 0 and
+// dz_j exactly 0 outside S).  Without the trait the kernel is the unmasked one,
+// instruction for instruction.
 //
 // LDS (HeadLayout, all of it dynamic; used by the kernel's carve and by the
 // launcher's byte count): action weights [AM][F], then the waves'
@@ -76,9 +84,17 @@ constexpr int64_t blocks(int M) { return ((int64_t)M + kWaves * kSPW - 1) / (kWa
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "vn_common.h"
 
 namespace head_loss {
+
+// the objective's kAllowed trait (false when it declares none)
+template <class Obj, class = void>
+struct has_allowed : std::false_type {};
+template <class Obj>
+struct has_allowed<Obj, std::void_t<decltype(Obj::kAllowed)>> : std::bool_constant<Obj::kAllowed> {};
 
 struct HeadArgs {
     const float *hp, *hv;       // latents [M][F] (row stride ldh)
@@ -189,23 +205,52 @@ __global__ __launch_bounds__(256) void head_loss_kernel(HeadArgs g, Obj obj) {
         for (int q = 0; q < Q; ++q) sv += dot4(hv[q], wvv[q]);
         const float v = gsum(sv) + bv;
         // log_softmax, entropy, argmax (uniform over the group)
-        f.zmax = f.z[0];
-        f.amax = 0;
+        unsigned allow = 0;
+        if constexpr (has_allowed<Obj>::value) {
+            // over the sample's allowed set only; an action outside it contributes
+            // selected zeros (no 0 * -inf), as a >= A does
+            allow = obj.allowed(s, A);
+            f.zmax = -INFINITY;
+            f.amax = 0;
+            bool found = false;
 #pragma unroll
-        for (int a = 1; a < AM; ++a) {
-            f.amax = f.z[a] > f.zmax ? a : f.amax;
-            f.zmax = fmaxf(f.zmax, f.z[a]);
-        }
-        float se = 0.0f;
+            for (int a = 0; a < AM; ++a) {
+                const bool in = (allow >> a) & 1u;
+                f.amax = in && (!found || f.z[a] > f.zmax) ? a : f.amax;
+                f.zmax = in ? fmaxf(f.zmax, f.z[a]) : f.zmax;
+                found = found || in;
+            }
+            float se = 0.0f;
 #pragma unroll
-        for (int a = 0; a < AM; ++a) se += a < A ? expf(f.z[a] - f.zmax) : 0.0f;
-        f.lse = logf(se);
-        f.ent = 0.0f;
+            for (int a = 0; a < AM; ++a) se += (allow >> a) & 1u ? expf(f.z[a] - f.zmax) : 0.0f;
+            f.lse = logf(se);
+            f.ent = 0.0f;
 #pragma unroll
-        for (int a = 0; a < AM; ++a) {
-            f.lpa[a] = f.z[a] - f.zmax - f.lse;
-            f.p[a] = a < A ? expf(f.lpa[a]) : 0.0f;
-            f.ent -= a < A ? f.p[a] * f.lpa[a] : 0.0f;
+            for (int a = 0; a < AM; ++a) {
+                const bool in = (allow >> a) & 1u;
+                f.lpa[a] = in ? f.z[a] - f.zmax - f.lse : (a < A ? 0.0f : -INFINITY);
+                f.p[a] = in ? expf(f.lpa[a]) : 0.0f;
+                f.ent -= in ? f.p[a] * f.lpa[a] : 0.0f;
+            }
+        } else {
+            f.zmax = f.z[0];
+            f.amax = 0;
+#pragma unroll
+            for (int a = 1; a < AM; ++a) {
+                f.amax = f.z[a] > f.zmax ? a : f.amax;
+                f.zmax = fmaxf(f.zmax, f.z[a]);
+            }
+            float se = 0.0f;
+#pragma unroll
+            for (int a = 0; a < AM; ++a) se += a < A ? expf(f.z[a] - f.zmax) : 0.0f;
+            f.lse = logf(se);
+            f.ent = 0.0f;
+#pragma unroll
+            for (int a = 0; a < AM; ++a) {
+                f.lpa[a] = f.z[a] - f.zmax - f.lse;
+                f.p[a] = a < A ? expf(f.lpa[a]) : 0.0f;
+                f.ent -= a < A ? f.p[a] * f.lpa[a] : 0.0f;
+            }
         }
         const float w = ok ? 1.0f : 0.0f;     // a padding pass contributes nothing
         obj.policy(blk, s, f, ok, w, inv_n);
@@ -220,7 +265,8 @@ __global__ __launch_bounds__(256) void head_loss_kernel(HeadArgs g, Obj obj) {
 #pragma unroll
         for (int a = 0; a < AM; ++a) {
             if (a >= A) break;
-            const float dz = obj.dz(s, f, a) + gent * f.p[a] * (f.lpa[a] + f.ent);
+            float dz = obj.dz(s, f, a) + gent * f.p[a] * (f.lpa[a] + f.ent);
+            if constexpr (has_allowed<Obj>::value) dz = (allow >> a) & 1u ? dz : 0.0f;
             gba[a] += dz;
 #pragma unroll
             for (int q = 0; q < Q; ++q) {

@@ -22,6 +22,7 @@ include/voxnav.h.  Public API:
   KickstartLearner / kickstart   PPO with a decaying cross-entropy to the planner's labels (imitate)
   normalize.RewardNormalizer   VecNormalize(norm_reward=True) on the rollout buffer, on the device
   checkpoint.save_reward_norm / load_reward_norm   its running statistics and returns (.npz)
+  masking.action_masks   invalid-action masks from CubicEnv observations (RolloutCollector / PPOLearner action_masks=True)
   sharding            multi-GPU agent sharding helpers
 """
 from . import rooms  # noqa: F401

@@ -109,6 +109,9 @@ _SIGS = {
     "vn_lstm_cell": (C.c_int, [P, C.c_int64, P, P, P, P, P, P, P, C.c_int32, C.c_int32, C.c_int32, P]),
     "vn_policy_head": (C.c_int, [P, P, C.c_int32, C.c_int32, P, P, C.c_int32, P, P, C.c_uint64, C.c_uint64,
                                  C.c_int64, C.c_int32, P, P, P, P]),
+    "vn_action_mask": (C.c_int, [P, C.c_int64, C.c_int32, P, P]),
+    "vn_policy_head_masked": (C.c_int, [P, P, C.c_int32, C.c_int32, P, P, C.c_int32, P, P, P, C.c_uint64, C.c_uint64,
+                                        C.c_int64, C.c_int32, P, P, P, P]),
     "vn_lstm_cell_masked": (C.c_int, [P, C.c_int64, P, P, P, P, P, P, P, C.c_int32, C.c_int32, C.c_int32, P]),
     "vn_lstm_cell_bf16": (C.c_int, [P, C.c_int64, P, P, P, P, P, P, P, P, C.c_int32, C.c_int32, C.c_int32, P]),
     "vn_policy_head_bf16": (C.c_int, [P, P, C.c_int32, C.c_int32, P, P, C.c_int32, P, P, C.c_uint64, C.c_uint64,
@@ -143,6 +146,9 @@ _SIGS = {
     "vn_ppo_loss_part_floats": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, P, P]),
     "vn_ppo_loss": (C.c_int, [P, P, C.c_int64, P, P, P, P, P, P, P, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                               C.c_float, C.c_float, C.c_int32, P, P, P, P, P, P, P, P]),
+    "vn_ppo_loss_masked_part_floats": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, P, P]),
+    "vn_ppo_loss_masked": (C.c_int, [P, P, C.c_int64, P, P, P, P, P, P, P, P, P, P, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_float, C.c_float, C.c_float, C.c_int32, P, P, P, P, P, P, P, P]),
     "vn_bc_loss_part_floats": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, P, P]),
     "vn_bc_loss": (C.c_int, [P, P, C.c_int64, P, P, P, P, P, P, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                              C.c_float, P, P, P, P, P, P, P]),

@@ -93,6 +93,14 @@ class RolloutBuffer:
     dones: Optional[torch.Tensor] = None
 
 
+@dataclass
+class MaskedRolloutBuffer(RolloutBuffer):
+    """A RolloutBuffer of a collector with ``action_masks=True``:
+    ``action_masks`` uint8 [T, N], bit a set iff action a would not have bumped
+    on ``obs[t]`` (``voxnav.masking``); every stored action lies inside its mask."""
+    action_masks: Optional[torch.Tensor] = None
+
+
 class _Weights:
     """The policy's parameters laid out for the collector's GEMMs/kernels.
 
@@ -224,12 +232,20 @@ class RolloutCollector:
     ``policy``: ``RecurrentActorCriticPolicy`` (PPO-LSTM, Grid_Train) or
     ``ActorCriticPolicy`` (PPO-MLP).  Its parameters are read at
     construction and again by ``sync_weights()`` (after a learner update).
+
+    ``action_masks=True`` (f32 collectors on a CubicEnv): invalid-action
+    masking.  Each step launches ``vn_action_mask`` on the obs the policy acts
+    on, into row t of a [T, N] uint8 buffer, and the action is drawn from the
+    allowed actions only (``vn_policy_head_masked``), so no executed action
+    bumps.  The MLPs then run layer by layer (``vn_linear_f32``) in front of the
+    masked head: the fused ``vn_mlp_head_f32`` has no mask and is bypassed.
+    ``collect()`` returns a ``MaskedRolloutBuffer``; ``act()`` masks too.
     """
 
     def __init__(self, env: BatchedGridEnv, policy, n_steps: int = 128, gamma: float = 0.99, gae_lambda: float = 0.95,
                  sample_seed: int = 42, deterministic: bool = False, store_lstm_states: bool = True,
                  reset_seed: int = 42, policy_dtype: str = "f32", monitor: bool = True,
-                 reward_norm: Optional[RewardNormalizer] = None):
+                 reward_norm: Optional[RewardNormalizer] = None, *, action_masks: bool = False):
         if not isinstance(policy, (ActorCriticPolicy, RecurrentActorCriticPolicy)):
             raise TypeError("policy must be an ActorCriticPolicy or RecurrentActorCriticPolicy")
         if getattr(policy, "obs_dim", OBS_DIM) != env.obs_dim:
@@ -258,6 +274,12 @@ class RolloutCollector:
             raise ValueError("policy_dtype must be 'f32' (the reference's) or 'bf16'")
         self.bf16 = policy_dtype == "bf16"
         self.cdt = torch.bfloat16 if self.bf16 else torch.float32
+        self.action_masks = bool(action_masks)
+        if self.action_masks:
+            if self.bf16:
+                raise ValueError("action_masks: the masked head is f32 only (policy_dtype='f32')")
+            if env.variant != _native.VN_VARIANT_CUBIC:
+                raise ValueError("action_masks: the mask is read off the CubicEnv observation (variant='cubic')")
         self._sp = None
         self.sync_weights()
         T, N, dev = self.n_steps, self.N, self.device
@@ -268,6 +290,8 @@ class RolloutCollector:
         self.rewards = z(T, N)
         self.values = z(T, N)
         self.log_probs = z(T, N)
+        self._masks = z(T, N, dt=torch.uint8) if self.action_masks else None
+        self._mask_row = None               # the masks of the step in flight
         self._term = z(N, dt=torch.uint8)
         self._trunc = z(N, dt=torch.uint8)
         self._tobs = z(N, env.obs_dim)
@@ -333,6 +357,8 @@ class RolloutCollector:
 
     def sync_weights(self):
         self.w = _Weights(self.policy, self.device, self.cdt)
+        if self.action_masks:
+            self.w.mlp_head = False        # vn_mlp_head_f32 draws unmasked: the layer kernels + the masked head
 
     def _stream(self):
         if self._sp is not None:       # inside collect(): the stream it started on
@@ -353,6 +379,12 @@ class RolloutCollector:
         w = self.w
         fn = self.lib.vn_policy_head_bf16 if self.bf16 else self.lib.vn_policy_head
         pi = lat_pi is not None
+        if pi and self.action_masks:
+            _native.check(self.lib.vn_policy_head_masked(
+                _p(lat_pi), _p(lat_vf), M, w.P, _p(w.wa), _p(w.ba), w.A, _p(w.wv), _p(w.bv), _p(self._mask_row),
+                self.sample_seed, t, self.env.agent_id_base, int(self.deterministic), _p(actions), _p(values),
+                _p(log_probs), self._stream()), "vn_policy_head_masked")
+            return
         _native.check(fn(_p(lat_pi), _p(lat_vf), M, w.P, _p(w.wa) if pi else None, _p(w.ba) if pi else None,
                          w.A if pi else 0, _p(w.wv), _p(w.bv), self.sample_seed if pi else 0, t if pi else 0,
                          self.env.agent_id_base if pi else 0, int(self.deterministic) if pi else 0, _p(actions),
@@ -432,6 +464,10 @@ class RolloutCollector:
     def _forward(self, obs: torch.Tensor, t: int, in_rollout: bool = False):
         """Policy step on obs [N, 80] into actions/values/log_probs[t]."""
         w, N = self.w, self.N
+        if self.action_masks:
+            self._mask_row = self._masks[t]
+            _native.check(self.lib.vn_action_mask(_p(obs), obs.stride(0), N, _p(self._mask_row), self._stream()),
+                          "vn_action_mask")
         if self.recurrent and self.fused:
             if in_rollout and self.store:
                 self._fused_rollout(obs, t)
@@ -640,10 +676,13 @@ class RolloutCollector:
             mon.harvest()
         hs = self._hs[:T] if self.recurrent and self.store else None
         cs = self._cs[:T] if self.recurrent and self.store else None
-        return RolloutBuffer(obs=self._obs[:T], actions=self.actions, rewards=self.rewards,
-                             episode_starts=self._starts[:T], values=self.values, log_probs=self.log_probs,
-                             advantages=adv, returns=ret, lstm_h=hs, lstm_c=cs, last_values=self._last_values,
-                             dones=self._starts[T])
+        fields = dict(obs=self._obs[:T], actions=self.actions, rewards=self.rewards,
+                      episode_starts=self._starts[:T], values=self.values, log_probs=self.log_probs,
+                      advantages=adv, returns=ret, lstm_h=hs, lstm_c=cs, last_values=self._last_values,
+                      dones=self._starts[T])
+        if self.action_masks:
+            return MaskedRolloutBuffer(action_masks=self._masks, **fields)
+        return RolloutBuffer(**fields)
 
     def _choose_actions(self, t: int) -> None:
         """Hook between the policy's forward pass and the env step of rollout

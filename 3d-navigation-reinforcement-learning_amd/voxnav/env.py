@@ -502,6 +502,14 @@ class BatchedGridEnv:
         _native.check(self.lib.vn_export_belief(self._h, _ptr(out), self._stream()), "vn_export_belief")
         return out
 
+    def action_masks(self, obs: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """uint8 [N]: bit a set iff action a taken on observation ``obs`` [N, 80]
+        would not bump (``voxnav.masking.action_masks``; CubicEnv variant only)."""
+        if self.variant != _native.VN_VARIANT_CUBIC:
+            raise ValueError("action masks are read off the CubicEnv observation (variant='cubic')")
+        from .masking import action_masks
+        return action_masks(obs, out)
+
     # ------------------------------------------------------- episode records
     def episode_records(self) -> torch.Tensor:
         """int64 [N, 12] (``_native.EPISODE_FIELDS``): per agent the totals

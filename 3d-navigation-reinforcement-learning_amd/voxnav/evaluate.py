@@ -35,15 +35,17 @@ from .env import BatchedGridEnv
 def evaluate_policy(policy, rooms, n_episodes: int = 10, local_map_length: int = 10, seed: int = 0,
                     device="cuda:0", variant: str = "cubic", crash_penalty: float = -2.0,
                     deterministic: bool = True, max_steps: Optional[int] = None,
-                    record_actions: bool = False) -> Dict[str, object]:
+                    record_actions: bool = False, action_masks: bool = False) -> Dict[str, object]:
     """Run ``n_episodes`` episodes in parallel; returns ``{"episodes": [...],
     "avg_score", "avg_bumps", "finished_pct", "avg_discovered", "avg_steps"}``
-    (plus ``"actions"`` [steps, n_episodes] when ``record_actions``)."""
+    (plus ``"actions"`` [steps, n_episodes] when ``record_actions``).
+    ``action_masks``: the policy picks among the actions that do not bump
+    (``RolloutCollector(action_masks=True)``; CubicEnv variant only)."""
     env = BatchedGridEnv(num_agents=n_episodes, rooms=rooms, local_map_length=local_map_length, autoreset=False,
                          device=device, crash_penalty=crash_penalty, variant=variant)
     try:
         col = RolloutCollector(env, policy, n_steps=1, deterministic=deterministic, store_lstm_states=False,
-                               reset_seed=seed, monitor=False)
+                               reset_seed=seed, monitor=False, action_masks=action_masks)
         dev = env.device
         obs = col._obs[0].clone()
         alive = torch.ones(n_episodes, dtype=torch.bool, device=dev)
@@ -126,8 +128,9 @@ class EvalCallback:
 
     def __init__(self, eval_rooms, eval_freq: int, n_eval_episodes: int = 10, deterministic: bool = True,
                  best_model_save_path=None, log_path=None, local_map_length: int = 10, seed: int = 1_000_000,
-                 crash_penalty: float = -2.0, device=None, verbose: int = 0):
+                 crash_penalty: float = -2.0, device=None, verbose: int = 0, action_masks: bool = False):
         self.rooms = eval_rooms
+        self.action_masks = bool(action_masks)
         self.eval_freq = int(eval_freq)
         self.n_eval_episodes = int(n_eval_episodes)
         self.deterministic = bool(deterministic)
@@ -155,7 +158,8 @@ class EvalCallback:
         r = evaluate_policy(policy, self.rooms, n_episodes=self.n_eval_episodes,
                             local_map_length=self.local_map_length,
                             seed=self.seed + len(self.evaluations_timesteps) * self.n_eval_episodes, device=dev,
-                            crash_penalty=self.crash_penalty, deterministic=self.deterministic)
+                            crash_penalty=self.crash_penalty, deterministic=self.deterministic,
+                            action_masks=self.action_masks)
         rewards = [round(e["score"], 6) for e in r["episodes"]]
         lengths = [int(e["steps"]) for e in r["episodes"]]
         self.evaluations_timesteps.append(int(num_timesteps))

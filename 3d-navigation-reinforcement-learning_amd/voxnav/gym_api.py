@@ -58,10 +58,12 @@ class GridAgent(EnvBase):
         self.rooms = [r.name for r in self._env.room_set.rooms] if self._env.room_set.use_room_draw else None
         self.total_free_cells = 1
         self._st = None
+        self._last_obs = None
 
     # ------------------------------------------------------------------ gym API
     def reset(self, seed: Optional[int] = None, options: Optional[dict] = None):
         obs = self._env.reset(seed=None if seed is None else [int(seed)])
+        self._last_obs = obs
         self._refresh()
         room = self._env.room_set.rooms[self._st["room"]]
         self.width, self.depth, self.height = room.shape
@@ -76,6 +78,7 @@ class GridAgent(EnvBase):
         if not self.action_space.contains(action):
             raise KeyError(action)   # the reference's action_map lookup (envs/CubicEnv.py:153)
         res = self._env.step([int(action)], reward_f64=True, terminal_obs=False)
+        self._last_obs = res.obs
         obs = res.obs[0].cpu().numpy()
         reward = np.float64(res.reward[0].item())
         self._refresh()
@@ -106,6 +109,15 @@ class GridAgent(EnvBase):
 
     def get_position(self):
         return (self.x, self.y, self.z)
+
+    def action_masks(self) -> np.ndarray:
+        """bool [6]: the actions that would not bump now, from the observation of
+        the last reset / step (sb3_contrib MaskablePPO's ``env.action_masks()``;
+        ``voxnav.masking``)."""
+        if self._last_obs is None:
+            raise RuntimeError("call reset() first")
+        from .masking import mask_to_bool
+        return mask_to_bool(self._env.action_masks(self._last_obs))[0].cpu().numpy()
 
     @property
     def last_episode(self) -> Optional[dict]:

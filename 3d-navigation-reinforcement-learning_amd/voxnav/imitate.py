@@ -126,6 +126,9 @@ class DaggerCollector(RolloutCollector):
                  beta: float = 1.0, mix_seed: int = 4242, labels: str = "action", **kwargs):
         if env.variant != _native.VN_VARIANT_CUBIC:
             raise ValueError("DaggerCollector: the frontier planner needs the CubicEnv variant")
+        if kwargs.get("action_masks"):
+            raise ValueError("DaggerCollector: action_masks is not supported (masked DAgger / kickstart: use "
+                             "RolloutCollector and PPOLearner)")
         info = env.info
         if info.pad_w > PLANNER_MAX_PAD or info.pad_d > PLANNER_MAX_PAD:
             raise ValueError(f"DaggerCollector: the frontier planner takes padded rooms of at most {PLANNER_MAX_PAD} x "

@@ -233,7 +233,8 @@ def _head_loss(name: str, h: torch.Tensor, action_net: torch.nn.Linear, value_ne
         raise ValueError(f"{name}: src must be [M] contiguous int64")
     npart, nspart = C.c_int64(), C.c_int64()
     sizes = ("vn_bc_loss_part_floats" if name.startswith("bc_") else
-             "vn_ppo_bc_loss_part_floats" if name.startswith("ppo_bc_") else "vn_ppo_loss_part_floats")
+             "vn_ppo_bc_loss_part_floats" if name.startswith("ppo_bc_") else
+             "vn_ppo_loss_masked_part_floats" if name == "ppo_loss_masked" else "vn_ppo_loss_part_floats")
     _native.check(getattr(lib, sizes)(M, F, A, C.byref(npart), C.byref(nspart)), sizes)
     dh = torch.empty((2, M, F), dtype=torch.float32, device=dev)
     gh = torch.empty(A * F + A + F + 1, dtype=torch.float32, device=dev)
@@ -268,6 +269,24 @@ def ppo_loss(h: torch.Tensor, action_net: torch.nn.Linear, value_net: torch.nn.L
     return _head_loss("ppo_loss", h, action_net, value_net, src,
                       ((actions, torch.int32), (advantages, torch.float32), (old_log_prob, torch.float32),
                        (returns, torch.float32)), "int32 actions / f32 values",
+                      (float(clip_range), float(ent_coef), float(vf_coef), int(bool(normalize_advantage))),
+                      adv_words=128)
+
+
+def ppo_loss_masked(h: torch.Tensor, action_net: torch.nn.Linear, value_net: torch.nn.Linear,
+                    src: Optional[torch.Tensor], actions: torch.Tensor, advantages: torch.Tensor,
+                    old_log_prob: torch.Tensor, returns: torch.Tensor, action_masks: torch.Tensor, clip_range: float,
+                    ent_coef: float, vf_coef: float, normalize_advantage: bool):
+    """``ppo_loss`` with invalid-action masking (csrc/voxnav_masked_loss.hip, the
+    formula in include/voxnav.h vn_ppo_loss_masked): ``action_masks`` uint8, a
+    flat rollout buffer like the others, bit j set where action j was allowed;
+    each sample's softmax, log-prob and entropy run over its allowed actions
+    (the taken one always among them), and the logits of the others get a
+    gradient of exactly 0.  Arguments, outputs and stats as ``ppo_loss``."""
+    return _head_loss("ppo_loss_masked", h, action_net, value_net, src,
+                      ((actions, torch.int32), (advantages, torch.float32), (old_log_prob, torch.float32),
+                       (returns, torch.float32), (action_masks, torch.uint8)),
+                      "int32 actions / f32 values / uint8 masks",
                       (float(clip_range), float(ent_coef), float(vf_coef), int(bool(normalize_advantage))),
                       adv_words=128)
 

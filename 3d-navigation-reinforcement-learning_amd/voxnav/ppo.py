@@ -35,6 +35,15 @@ With ``process_group`` set, gradients are averaged over the ranks (one
 flattened all-reduce per minibatch, RCCL over xGMI with the nccl backend)
 before the clip -- data-parallel training over agent shards.
 
+``action_masks=True`` trains on a ``MaskedRolloutBuffer`` (a collector with
+``action_masks=True``; sb3_contrib ``MaskablePPO.train``): every sample's
+softmax, log-prob and entropy run over its allowed actions ``S`` -- its mask
+with the taken action added, an empty set counting as full -- in the fused
+masked kernel (``learn_ops.ppo_loss_masked``, csrc/voxnav_masked_loss.hip)
+where the fused loss runs, else through torch autograd of the same formula:
+logits ``masked_fill(~S, -inf)``, ``log_softmax``, the entropy with the masked
+terms zeroed (also the CPU path).
+
 The minibatch order is drawn from ``numpy.random.default_rng(seed)``
 (sb3 uses the global numpy generator) or passed explicitly as
 ``epoch_orders`` (what the parity tests do with ``oracle/ppo_oracle.py``).
@@ -57,7 +66,7 @@ from .policy import ActorCriticPolicy, RecurrentActorCriticPolicy
 class PPOLearner:
     def __init__(self, policy, learning_rate: float = 3e-4, n_epochs: int = 10, batch_size: int = 64,
                  clip_range: float = 0.2, ent_coef: float = 0.01, vf_coef: float = 0.5, max_grad_norm: float = 0.5,
-                 normalize_advantage: bool = True, seed: int = 0, process_group=None):
+                 normalize_advantage: bool = True, seed: int = 0, process_group=None, action_masks: bool = False):
         if not isinstance(policy, (ActorCriticPolicy, RecurrentActorCriticPolicy)):
             raise TypeError("policy must be an ActorCriticPolicy or RecurrentActorCriticPolicy")
         if batch_size < 1 or n_epochs < 1:
@@ -72,6 +81,8 @@ class PPOLearner:
         self.vf_coef = float(vf_coef)
         self.max_grad_norm = float(max_grad_norm)
         self.normalize_advantage = bool(normalize_advantage)
+        self.action_masks = bool(action_masks)
+        self.masked_fused_updates = 0   # minibatches that went through learn_ops.ppo_loss_masked
         self.rng = np.random.default_rng(seed)
         self.group = process_group
         self.params = [p for p in policy.parameters() if p.requires_grad]
@@ -126,7 +137,7 @@ class PPOLearner:
             g.copy_(flat[o:o + n].view_as(g))
             o += n
 
-    def _heads(self, lat_pi, lat_vf, actions, lat_pair=None):
+    def _heads(self, lat_pi, lat_vf, actions, lat_pair=None, masks=None):
         pol = self.policy
         # both MLP branches layer by layer and the heads on the f32 matrix
         # cores (voxnav/learn_ops.py; torch's own ops on the CPU)
@@ -135,7 +146,18 @@ class PPOLearner:
                                         x_pair=lat_pair)
         logits = learn_ops.linear(h_pi, pol.action_net)
         values = learn_ops.linear(h_vf, pol.value_net).flatten()
+        if masks is not None:
+            # the allowed set: the mask's bits, the taken action, and everything when that is empty
+            A = logits.shape[-1]
+            ar = torch.arange(A, device=masks.device)
+            S = ((masks.view(-1, 1).to(torch.int64) >> ar) & 1).bool()
+            S = S | (ar.view(1, A) == actions.view(-1, 1))
+            S = S | ~S.any(-1, keepdim=True)
+            logits = logits.masked_fill(~S, float("-inf"))
         logp_all = torch.log_softmax(logits, dim=-1)
+        if masks is not None:
+            # a masked action's terms are zeros (exp(0) 0 in the entropy), and it gets no gradient
+            logp_all = torch.where(S, logp_all, logp_all.new_zeros(()))
         log_prob = logp_all.gather(1, actions.view(-1, 1)).flatten()
         entropy = -(logp_all.exp() * logp_all).sum(-1)
         return values, log_prob, entropy
@@ -282,10 +304,17 @@ class PPOLearner:
         obs = buf.obs.reshape(T * N, -1)[src]
         return (obs, obs, None), src
 
+    def _check_masks(self, buf) -> None:
+        """``train`` and ``update`` refuse a buffer without masks when the learner masks."""
+        if self.action_masks and getattr(buf, "action_masks", None) is None:
+            raise ValueError("PPOLearner(action_masks=True) needs the buffer's action_masks "
+                             "(RolloutCollector(action_masks=True))")
+
     def update(self, buf, idx: torch.Tensor, packed: Optional[dict] = None) -> torch.Tensor:
         """One minibatch (env-major flat ids ``idx``): losses, backward,
         (all-reduce), clip, Adam.  Returns the logged values as a device
         tensor (no host sync beyond the recurrent minibatch's size)."""
+        self._check_masks(buf)
         if self.recurrent:
             (lat_pi, lat_vf, lat_pair), src = self._evaluate_recurrent(buf, packed or self._pack_begin(buf, idx))
         else:
@@ -300,7 +329,8 @@ class PPOLearner:
                                        x_pair=lat_pair, stacked=True)
                 if h is not None:
                     return self._update_fused(buf, h, src, norm)
-        values, log_prob, entropy = self._heads(lat_pi, lat_vf, buf.actions.reshape(-1)[src].long(), lat_pair)
+        masks = buf.action_masks.reshape(-1)[src] if self.action_masks else None
+        values, log_prob, entropy = self._heads(lat_pi, lat_vf, buf.actions.reshape(-1)[src].long(), lat_pair, masks)
         adv = buf.advantages.reshape(-1)[src]
         if norm:
             adv = (adv - adv.mean()) / (adv.std() + 1e-8)
@@ -331,6 +361,14 @@ class PPOLearner:
         their gradient in the fused loss kernel (learn_ops.ppo_loss), then
         ``_step_fused``."""
         pol = self.policy
+        if self.action_masks:
+            dh, grads, stats = learn_ops.ppo_loss_masked(h, pol.action_net, pol.value_net, src,
+                                                         buf.actions.reshape(-1), buf.advantages.reshape(-1),
+                                                         buf.log_probs.reshape(-1), buf.returns.reshape(-1),
+                                                         buf.action_masks.reshape(-1), self.clip_range,
+                                                         self.ent_coef, self.vf_coef, norm)
+            self.masked_fused_updates += 1
+            return self._step_fused(h, dh, grads, stats)
         dh, grads, stats = learn_ops.ppo_loss(h, pol.action_net, pol.value_net, src, buf.actions.reshape(-1),
                                               buf.advantages.reshape(-1), buf.log_probs.reshape(-1),
                                               buf.returns.reshape(-1), self.clip_range, self.ent_coef, self.vf_coef,
@@ -451,6 +489,7 @@ class PPOLearner:
     def train(self, buf, epoch_orders: Optional[Sequence] = None) -> Dict[str, float]:
         """One ``train()`` over a collector ``RolloutBuffer`` (n_epochs passes).
         Returns the means of sb3's logged quantities."""
+        self._check_masks(buf)
         m, n_mb = self._run_epochs(buf, epoch_orders)
         return dict(policy_gradient_loss=m[0], value_loss=m[1], entropy_loss=m[2], loss=m[3], approx_kl=m[4],
                     clip_fraction=m[5], grad_norm=m[6], explained_variance=self._explained_variance(buf),

@@ -216,6 +216,15 @@ class VoxnavVecEnv(_VecEnvBase):
         self.step_async(actions)
         return self.step_wait()
 
+    def action_masks(self) -> np.ndarray:
+        """bool [N, 6]: per env the actions that would not bump now, from the
+        observations of the last reset / step (sb3_contrib MaskablePPO's
+        ``env.action_masks()``; ``voxnav.masking``, CubicEnv variant only)."""
+        if not self._reset_done:
+            raise RuntimeError("call reset() first")
+        from .masking import mask_to_bool
+        return mask_to_bool(self.env.action_masks(self._obs)).cpu().numpy()
+
     def close(self) -> None:
         if not self.closed:
             self.env.close()
@@ -262,6 +271,9 @@ class VoxnavVecEnv(_VecEnvBase):
             return [(int(st["x"][i]), int(st["y"][i]), int(st["z"][i])) for i in idx]
         if method_name == "render":
             return [None] * len(idx)
+        if method_name == "action_masks":      # what sb3_contrib's get_action_masks calls
+            m = self.action_masks()
+            return [m[i] for i in idx]
         raise AttributeError(f"VoxnavVecEnv envs have no method {method_name!r}")
 
     def env_is_wrapped(self, wrapper_class, indices=None) -> List[bool]:

@@ -713,6 +713,44 @@ int vn_policy_head_bf16(const uint16_t *latent_pi, const uint16_t *latent_vf, in
                         int32_t deterministic, int32_t *actions, float *values, float *log_probs, void *stream);
 
 /*
+ * Invalid-action masking (Huang & Ontanon 2020; sb3_contrib MaskablePPO's
+ * env.action_masks()), CubicEnv only (csrc/voxnav_mask.hip).
+ *
+ * vn_action_mask: mask [N] uint8 from obs f32 [N][80] (row stride ldo >= 80
+ * floats).  Bit a (0 fwd, 1 right, 2 back, 3 left, 4 up, 5 down) is set iff
+ * action a taken now would not bump; bits 6 and 7 are 0.  With f the index of
+ * the 1 in obs[64:68] (the facing one-hot, 0 when there is none):
+ *   a < 4: (dx, dy) = the step of relative direction a under facing f
+ *          (N: fwd +y, right +x, back -y, left -x; E, S, W: that ring turned
+ *          once, twice, three times), dz = 0;  a = 4: dz = +1;  a = 5: dz = -1
+ *   v = obs[(dx+2) 16 + (dy+2) 4 + (dz+2)]   (the 4x4x4 window, offsets -2..+1
+ *          around the centre 42: cells 58 / 26 (+-x), 46 / 38 (+-y), 43 / 41 (+-z))
+ *   blocked iff v == 0.0f (known wall: (-2 + 2) / 22) or v == 1.0f / 22.0f
+ *          (the window's out-of-bounds code -1)
+ * The mask is exact: get_obs casts a ray of length >= 1 in all six directions
+ * before it builds the window (envs/CubicEnv.py:229-275), so every in-bounds
+ * neighbour is known wall or known free when the window is read (:322-332),
+ * and the window reads -1 only out of bounds.  One launch, stream-ordered, no
+ * host sync.  VN_ERR_INVALID without a launch: a NULL pointer, N < 1, ldo < 80.
+ *
+ * vn_policy_head_masked: vn_policy_head (f32) with the draw restricted to the
+ * allowed actions S = mask & (2^n_actions - 1) of each agent (mask [N] uint8,
+ * required, as is latent_pi; S = 0 counts as all allowed).  Logits outside S
+ * take no part in the max, the log-sum-exp or the cdf; sampling takes the
+ * first allowed a with u < cdf[a], the cdf running over the allowed actions in
+ * index order, and the highest allowed index when none crosses; deterministic:
+ * the argmax over S, the lowest index on ties.  log_prob = z[act] - lse_S.
+ * The Philox counter and key are vn_policy_head's; values do not depend on
+ * the mask; with S full, actions, log_probs and values are vn_policy_head's
+ * bits.  Sizes and refusals as vn_policy_head.
+ */
+int vn_action_mask(const float *obs, int64_t ldo, int32_t N, uint8_t *mask, void *stream);
+int vn_policy_head_masked(const float *latent_pi, const float *latent_vf, int32_t N, int32_t P, const float *w_action,
+                          const float *b_action, int32_t n_actions, const float *w_value, const float *b_value,
+                          const uint8_t *mask, uint64_t sample_seed, uint64_t t, int64_t agent_id_base,
+                          int32_t deterministic, int32_t *actions, float *values, float *log_probs, void *stream);
+
+/*
  * The collector's whole policy after the LSTM in ONE launch: the pi and vf
  * MLPs (MlpExtractor, Linear + Tanh per layer; net_arch [256, 256, 128],
  * train/Grid_Train.py:68-80) and the heads + Categorical draw of
@@ -936,6 +974,28 @@ int vn_ppo_loss(const float *hp, const float *hv, int64_t ldh, const float *wa, 
                 const float *old_log_prob, const float *returns, int32_t M, int32_t F, int32_t A, float clip_range,
                 float ent_coef, float vf_coef, int32_t normalize_advantage, float *dhp, float *dhv, float *grad_heads,
                 double *stats, double *adv_sums, float *part, double *spart, void *stream);
+
+/* vn_ppo_loss with invalid-action masking (csrc/voxnav_masked_loss.hip;
+ * sb3_contrib MaskablePPO.train): mask uint8, indexed by src like the other
+ * buffers, bit j set where action j was allowed (vn_action_mask of the sample's
+ * observation).  With S_i = (mask_i & (2^A - 1)) | (1 << a_i) -- the taken
+ * action always counts as allowed, an empty set as full --
+ *   lp_ij = z_ij - logsumexp_{k in S_i} z_ik   (j in S_i)
+ *   p_ij  = exp(lp_ij)                         (j in S_i), 0 otherwise
+ *   H_i   = -sum_{j in S_i} p_ij lp_ij
+ *   dz_ij = g_lp_i ([j = a_i] - p_ij) + (ent_coef / M) p_ij (lp_ij + H_i)
+ *                                              (j in S_i), exactly 0 otherwise
+ * Everything else is vn_ppo_loss's: the ratio, the clip, the advantage
+ * normalisation, the value term, stats [6], grad_heads, the workspaces (sizes
+ * from vn_ppo_loss_masked_part_floats), the launches and the refusals, plus a
+ * NULL mask.  With every S_i full the outputs are vn_ppo_loss's bits. */
+int vn_ppo_loss_masked_part_floats(int32_t M, int32_t F, int32_t A, int64_t *n_part, int64_t *n_spart);
+int vn_ppo_loss_masked(const float *hp, const float *hv, int64_t ldh, const float *wa, const float *ba,
+                       const float *wv, const float *bv, const int64_t *src, const int32_t *actions,
+                       const float *advantages, const float *old_log_prob, const float *returns, const uint8_t *mask,
+                       int32_t M, int32_t F, int32_t A, float clip_range, float ent_coef, float vf_coef,
+                       int32_t normalize_advantage, float *dhp, float *dhv, float *grad_heads, double *stats,
+                       double *adv_sums, float *part, double *spart, void *stream);
 
 /* Behaviour-cloning minibatch loss + its gradient to the MLP latents
  * (csrc/voxnav_bc_loss.hip), the counterpart of vn_ppo_loss for the DAgger warm

@@ -1,0 +1,141 @@
+#!/usr/bin/env python3
+"""What invalid-action masking costs, in one process:
+
+loss    vn_ppo_loss_masked against vn_ppo_loss (csrc/voxnav_masked_loss.hip, csrc/voxnav_ppo_loss.hip)
+        at the learner bench's minibatch: M = 65,536 samples, A = 6, F in {128, 256}, gathered through
+        src from buffers of 2 M rows, normalised advantages -- same latents, heads, rows and buffers;
+        the method of scripts/bc_loss_bench.py (HIP events around --batch calls back to back, median of
+        --reps repetitions after --warmup, the case list --rounds times in turn).  The masks are random
+        with the taken action allowed (about half of the other actions forbidden); ``full`` is the
+        masked kernel under all-allowed masks.
+collect the C3 (PPO-MLP, P2_training) and C4 (PPO-LSTM f32, P3_training) collectors of bench.py at
+        --agents agents, --T steps: ``action_masks`` off (the fused vn_mlp_head_f32), on (vn_action_mask
+        + vn_linear_f32 per layer + vn_policy_head_masked), and off with the fused head disabled too
+        (VOXNAV_MLP_HEAD=0: the unfused path without masks, which splits the gap into "unfused" and
+        "mask"); one untimed rollout, then --rollouts timed ones, the three collectors in turn
+        --rounds times.  The bumps that the timed rollouts saw are reported beside.
+
+Prints one JSON line.  Nothing is bounded here.  Needs a GPU."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+from pathlib import Path
+
+REPO = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(REPO / "3d-navigation-reinforcement-learning_amd"))
+sys.path.insert(0, str(REPO / "scripts"))
+import torch  # noqa: E402
+
+from bc_loss_bench import timed  # noqa: E402
+from voxnav.learn_ops import ppo_loss, ppo_loss_masked  # noqa: E402
+
+
+def loss_leg(args, dev):
+    M, A = args.M, args.A
+    torch.manual_seed(0)
+    R = 2 * M
+    src = torch.randperm(R, device=dev)[:M].contiguous()
+    act = torch.randint(0, A, (R,), device=dev, dtype=torch.int32)
+    adv, olp, ret = torch.randn(R, device=dev), torch.randn(R, device=dev) - 1.8, torch.randn(R, device=dev)
+    masks = ((1 << act) | torch.randint(0, 1 << A, (R,), device=dev)).to(torch.uint8)
+    full = torch.full((R,), (1 << A) - 1, dtype=torch.uint8, device=dev)
+    out = {}
+    for F in args.widths:
+        an, vn = torch.nn.Linear(F, A).to(dev), torch.nn.Linear(F, 1).to(dev)
+        h = torch.tanh(torch.randn((2, M, F), device=dev))
+        cases = {
+            "ppo_loss": lambda: ppo_loss(h, an, vn, src, act, adv, olp, ret, 0.2, 0.01, 0.5, True),
+            "ppo_loss_masked": lambda: ppo_loss_masked(h, an, vn, src, act, adv, olp, ret, masks, 0.2, 0.01, 0.5, True),
+            "ppo_loss_masked_full": lambda: ppo_loss_masked(h, an, vn, src, act, adv, olp, ret, full, 0.2, 0.01, 0.5,
+                                                            True),
+        }
+        rounds = [{k: timed(fn, args.reps, args.warmup, dev, args.batch) for k, fn in cases.items()}
+                  for _ in range(args.rounds)]
+        r = rounds[0]
+        for k in cases:
+            med = [x[k]["median_ms"] for x in rounds]
+            r[k]["rounds_median_ms"] = med
+            r[k]["ratio_to_ppo_loss"] = round(statistics.median(med) /
+                                              statistics.median([x["ppo_loss"]["median_ms"] for x in rounds]), 4)
+        out[str(F)] = r
+    return out
+
+
+def collect_leg(args, dev, kind):
+    from voxnav.collector import RolloutCollector
+    from voxnav.env import BatchedGridEnv
+    from voxnav.policy import ActorCriticPolicy, RecurrentActorCriticPolicy
+    from voxnav.rooms import load_archive_set
+    rooms = load_archive_set("P3_training" if kind == "lstm" else "P2_training")
+    torch.manual_seed(42)
+    pol = (RecurrentActorCriticPolicy() if kind == "lstm" else ActorCriticPolicy()).to(dev)
+    N, T = args.agents, args.T
+    cols = {}
+    prev = os.environ.get("VOXNAV_MLP_HEAD")                            # the caller's value is put back below
+    for name, masks, fused_head in (("off", False, True), ("on", True, True), ("off_unfused", False, False)):
+        env = BatchedGridEnv(num_agents=N, rooms=rooms, local_map_length=args.L, autoreset=True, device=dev)
+        os.environ["VOXNAV_MLP_HEAD"] = "1" if fused_head else "0"      # read when the weights are laid out
+        col = RolloutCollector(env, pol, n_steps=T, sample_seed=42, reset_seed=42, action_masks=masks)
+        if prev is None:
+            os.environ.pop("VOXNAV_MLP_HEAD")
+        else:
+            os.environ["VOXNAV_MLP_HEAD"] = prev
+        col.collect()
+        cols[name] = (env, col)
+    res = {name: {"mlp_head": bool(col.w.mlp_head), "ms_per_step": []} for name, (_, col) in cols.items()}
+    for _ in range(args.rounds):
+        for name, (env, col) in cols.items():
+            b0 = int(env.episode_totals()[3]) + int(env.state()["bump_count"].sum())
+            torch.cuda.synchronize(dev)
+            t0 = time.perf_counter()
+            for _ in range(args.rollouts):
+                col.collect()
+            torch.cuda.synchronize(dev)
+            el = time.perf_counter() - t0
+            res[name]["ms_per_step"].append(round(el * 1e3 / (T * args.rollouts), 4))
+            b1 = int(env.episode_totals()[3]) + int(env.state()["bump_count"].sum())
+            # ended episodes' bumps are in the totals, the running ones' in the state: an exact count
+            res[name].setdefault("bumps_seen", []).append(b1 - b0)
+    for name, (env, _) in cols.items():
+        r = res[name]
+        r["median_ms_per_step"] = statistics.median(r["ms_per_step"])
+        r["env_steps_per_s"] = round(N * 1e3 / r["median_ms_per_step"], 1)
+        env.close()
+    off = res["off"]["median_ms_per_step"]
+    res["on_over_off"] = round(res["on"]["median_ms_per_step"] / off, 4)
+    res["off_unfused_over_off"] = round(res["off_unfused"]["median_ms_per_step"] / off, 4)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--legs", default="loss,collect")
+    ap.add_argument("--M", type=int, default=65536)
+    ap.add_argument("--A", type=int, default=6)
+    ap.add_argument("--widths", type=int, nargs="+", default=[128, 256])
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--batch", type=int, default=16)
+    ap.add_argument("--agents", type=int, default=65536)
+    ap.add_argument("--T", type=int, default=128)
+    ap.add_argument("--L", type=int, default=10)
+    ap.add_argument("--rollouts", type=int, default=2)
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("mask_bench.py needs a GPU")
+    dev = torch.device("cuda:0")
+    res = {"args": vars(args)}
+    legs = args.legs.split(",")
+    if "loss" in legs:
+        res["loss"] = loss_leg(args, dev)
+    if "collect" in legs:
+        res["collect"] = {"C3_mlp": collect_leg(args, dev, "mlp"), "C4_lstm": collect_leg(args, dev, "lstm")}
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()

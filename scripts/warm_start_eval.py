@@ -12,7 +12,10 @@ short actions (vn_plan_frontier_dists, vn_bc_loss_set) instead of its lowest-k a
 --then ppo | kickstart --then-iterations K: after the warm start, K more iterations
 on the same collector at beta = 0 with a fresh learner of the reference's PPO hyperparameters --
 plain ``ppo.learn``, or ``imitate.kickstart`` with bc_coef = --bc-decay ^ iteration -- and one more
-table row for the policy after them.  Prints the per-iteration rows, the table and one JSON line.
+table row for the policy after them.  --action-masks (with --then ppo): the then-phase
+collects with invalid-action masking -- a ``RolloutCollector(action_masks=True)`` on the same env (the
+DAgger collector has no masks; it starts from a fresh reset), ``PPOLearner(action_masks=True)`` -- and
+its table row is evaluated with masks too.  Prints the per-iteration rows, the table and one JSON line.
 Needs a GPU."""
 import argparse
 import json
@@ -24,6 +27,7 @@ REPO = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(REPO / "3d-navigation-reinforcement-learning_amd"))
 import torch  # noqa: E402
 
+from voxnav.collector import RolloutCollector  # noqa: E402
 from voxnav.env import BatchedGridEnv  # noqa: E402
 from voxnav.evaluate import RESULTS_HEADER, evaluate_policy, results_table_row  # noqa: E402
 from voxnav.imitate import BCLearner, DaggerCollector, KickstartLearner, kickstart, warm_start  # noqa: E402
@@ -59,7 +63,11 @@ def main():
                     help="after the warm start: plain PPO, or PPO with the decaying cross-entropy (DESIGN.md 10.7)")
     ap.add_argument("--then-iterations", type=int, default=8)
     ap.add_argument("--bc-decay", type=float, default=0.7, help="kickstart: bc_coef = bc_decay ^ iteration")
+    ap.add_argument("--action-masks", action="store_true",
+                    help="--then ppo with invalid-action masking, evaluated with masks too (DESIGN.md 10.8)")
     args = ap.parse_args()
+    if args.action_masks and args.then != "ppo":
+        raise SystemExit("--action-masks goes with --then ppo")
     if not torch.cuda.is_available():
         raise SystemExit("warm_start_eval.py needs a GPU")
     dev = "cuda:0"
@@ -106,11 +114,22 @@ def main():
             then_hist = kickstart(col, kl, total_timesteps=steps, bc_coef=lambda i: args.bc_decay ** i,
                                   callback=show_then)
             print(f"kickstart: fused loss minibatches {kl.fused_updates} of {kl.n_updates}")
+        elif args.action_masks:
+            mcol = RolloutCollector(env, pol, n_steps=args.n_steps, reward_norm=rnorm, action_masks=True)
+            ml = PPOLearner(pol, action_masks=True, **hyper)
+            then_hist = learn(mcol, ml, total_timesteps=steps, callback=show_then)
+            print(f"masked ppo: fused masked loss minibatches {ml.masked_fused_updates} of {ml.n_updates}")
         else:
             then_hist = learn(col, PPOLearner(pol, **hyper), total_timesteps=steps, callback=show_then)
         torch.cuda.synchronize()
         then_s = time.time() - t1
-        rows[f"warm start, then {args.then_iterations} x {args.then}" + tag] = evaluate_policy(pol, eval_rooms, **kw)
+        if args.action_masks:
+            rows[f"warm start, then {args.then_iterations} x masked ppo, masked evaluation" + tag] = \
+                evaluate_policy(pol, eval_rooms, action_masks=True, **kw)
+            rows["the same policy, unmasked evaluation" + tag] = evaluate_policy(pol, eval_rooms, **kw)
+        else:
+            rows[f"warm start, then {args.then_iterations} x {args.then}" + tag] = evaluate_policy(pol, eval_rooms,
+                                                                                                 **kw)
     env.close()
     rows["frontier planner"] = evaluate_planner(eval_rooms, **kw)
     print(f"warm start: {len(hist)} iterations, {hist[-1]['num_timesteps']} env steps, {train_s:.1f} s "
