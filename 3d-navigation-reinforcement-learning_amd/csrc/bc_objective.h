@@ -1,8 +1,9 @@
 // bc_objective.h -- what is behaviour cloning's of the head loss (head_loss.h:
 // what an objective supplies): the labelled count of the minibatch and the two
 // cross-entropy objectives BcLabel / BcSet on BcCommon.  voxnav_bc_loss.hip
-// states the formulas; vn_bc_loss / vn_bc_loss_set (there) and vn_ppo_bc_loss /
-// vn_ppo_bc_loss_set (voxnav_ppo_bc_loss.hip) use them.
+// states the formulas; vn_bc_loss / vn_bc_loss_set (there), vn_ppo_bc_loss /
+// vn_ppo_bc_loss_set (voxnav_ppo_bc_loss.hip) and their masked forms
+// (masked_bc_objective.h) use them.
 // Unit-local (an anonymous namespace): each unit instantiates its own kernels.
 #pragma once
 

@@ -1,9 +1,10 @@
 // head_loss.h -- the fused "head loss" of the learner, once: the skeleton that
 // vn_ppo_loss (voxnav_ppo_loss.hip), vn_bc_loss / vn_bc_loss_set
 // (voxnav_bc_loss.hip), vn_ppo_bc_loss / vn_ppo_bc_loss_set
-// (voxnav_ppo_bc_loss.hip) and vn_ppo_loss_masked (voxnav_masked_loss.hip)
-// share; their file headers state the formulas.  Common
-// to them, with lp = log_softmax(z), p = exp(lp), H the entropy:
+// (voxnav_ppo_bc_loss.hip), vn_ppo_loss_masked (voxnav_masked_loss.hip) and
+// the masked cross-entropy entries (voxnav_masked_bc_loss.hip,
+// voxnav_masked_ppo_bc_loss.hip) share; their file headers state the formulas.
+// Common to them, with lp = log_softmax(z), p = exp(lp), H the entropy:
 //   dz_j = (the objective's policy term)_j + (ent_coef / M) p_j (lp_j + H)
 //   dv   = vf_coef 2 (v - ret) / M
 //
@@ -17,7 +18,7 @@
 // squared value error, slot 2 the entropy), and the reduce kernel that sums the
 // partials in a fixed order.  An objective (a plain struct: PpoClip in
 // ppo_objective.h, BcLabel / BcSet in bc_objective.h, PpoBc<> composed of them
-// in voxnav_ppo_bc_loss.hip) supplies what differs:
+// in ppo_bc_objective.h) supplies what differs:
 //   kStats            f64 sums per block (slots 0, 3.. are the objective's)
 //   begin(M)          block-uniform values, every thread (e.g. 1 / labelled) -> Obj::Block
 //   gather(b, r, A)   the sample's own gathered inputs -> Obj::Sample
@@ -29,7 +30,8 @@
 //   static constexpr bool kAllowed = true;   allowed(s, A) -> bits of the sample's
 //                     allowed actions, a non-empty subset of bits 0 .. A-1
 // has the softmax, entropy and argmax run over that set only (PpoClipMasked in
-// voxnav_masked_loss.hip: lp_j = z_j - logsumexp_{k in S} z_k, p_j = 0 and
+// voxnav_masked_loss.hip, BcMasked<> in masked_bc_objective.h, PpoBcMasked<> in
+// voxnav_masked_ppo_bc_loss.hip: lp_j = z_j - logsumexp_{k in S} z_k, p_j = 0 and
 // dz_j exactly 0 outside S).  Without the trait the kernel is the unmasked one,
 // instruction for instruction.
 //

@@ -21,11 +21,12 @@
 // and the gradients equal vn_bc_loss's.  n = 0: the cross-entropy, its
 // gradient and the accuracy are exactly 0.
 //
-// The objective PpoBc<Bc> is composed of PpoClip (ppo_objective.h) and BcLabel
-// or BcSet (bc_objective.h): their members run as they are, on their own parts
-// of the block and sample records.  f64 sums per block [7]: PPO's five
-// (surrogate, squared value error, entropy, kl, clipped), the cross-entropy,
-// the correct argmax.
+// The objective PpoBc<Bc> (ppo_bc_objective.h) is composed of PpoClip
+// (ppo_objective.h) and BcLabel or BcSet (bc_objective.h): their members run as
+// they are, on their own parts of the block and sample records (the masked
+// forms, voxnav_masked_ppo_bc_loss.hip, compose it too).  f64 sums per block
+// [7]: PPO's five (surrogate, squared value error, entropy, kl, clipped), the
+// cross-entropy, the correct argmax.
 //
 // Launches: (1) adv_sum_kernel when normalize_advantage; (2) bc_count_kernel
 // with weights or sets (each loss block folds the 64 pairs, then the 64 counts,
@@ -42,66 +43,13 @@
 
 #include "bc_objective.h"
 #include "head_loss.h"
+#include "ppo_bc_objective.h"
 #include "ppo_objective.h"
 #include "vn_common.h"
 
 using vn_detail::fail;
 
 namespace {
-
-template <class Bc>
-struct PpoBc {
-    static constexpr int kStats = 7;
-    PpoClip ppo;
-    Bc bc;
-    float bc_coef;
-    struct Block {
-        PpoClip::Block p;
-        typename Bc::Block b;
-    };
-    struct Sample {
-        PpoClip::Sample p;
-        typename Bc::Sample b;
-    };
-
-    __device__ __forceinline__ Block begin(int M) const { return {ppo.begin(M), bc.begin(M)}; }
-    __device__ __forceinline__ Sample gather(const Block &b, int64_t r, int A) const {
-        return {ppo.gather(b.p, r, A), bc.gather(b.b, r, A)};
-    }
-    template <int AM>
-    __device__ __forceinline__ void policy(const Block &b, Sample &s, const head_loss::Forward<AM> &f, bool ok, float w,
-                                           float inv_n) const {
-        ppo.policy(b.p, s.p, f, ok, w, inv_n);
-        bc.policy(b.b, s.b, f, ok, w, inv_n);
-        s.b.gce *= bc_coef;     // bc_coef = 1: the cross-entropy's own scale, bit for bit
-    }
-    template <int AM>
-    __device__ __forceinline__ float dz(const Sample &s, const head_loss::Forward<AM> &f, int a) const {
-        return ppo.dz(s.p, f, a) + bc.dz(s.b, f, a);
-    }
-    // PPO's slots are the block's 0, 3, 4; the cross-entropy objective's 0 and 3 land in 5 and 6
-    template <int AM>
-    __device__ __forceinline__ void stats(const Sample &s, const head_loss::Forward<AM> &f, double *st) const {
-        ppo.stats(s.p, f, st);
-        double t[BcCommon::kStats] = {0.0, 0.0, 0.0, 0.0};
-        bc.stats(s.b, f, t);
-        st[5] += t[0];
-        st[6] += t[3];
-    }
-    // stats [9] = vn_ppo_loss's six (the loss with bc_coef ce added), cross-entropy, accuracy, labelled share
-    __device__ __forceinline__ void finish(const double *v, int M, float ent_coef, float vf_coef,
-                                           double *stats) const {
-        double p[6], b[6];
-        ppo.finish(v, M, ent_coef, vf_coef, p);
-        const double vb[BcCommon::kStats] = {v[5], v[1], v[2], v[6]};
-        bc.finish(vb, M, ent_coef, vf_coef, b);
-        p[3] = p[3] + (double)bc_coef * b[0];
-        for (int k = 0; k < 6; ++k) stats[k] = p[k];
-        stats[6] = b[0];
-        stats[7] = b[4];
-        stats[8] = b[5];
-    }
-};
 
 // vn_ppo_bc_loss (Bc = BcLabel, int32 labels) and vn_ppo_bc_loss_set (BcSet, uint8 label sets)
 template <class Bc, class Label>

@@ -22,6 +22,12 @@ Online Learning", AISTATS 2011):
   coefficient that the loop lets decay to 0 (Schmitt et al., "Kickstarting
   Deep Reinforcement Learning", 2018), through the fused
   kernel ``learn_ops.ppo_bc_loss`` (csrc/voxnav_ppo_bc_loss.hip).
+* ``MaskedDaggerCollector`` / ``MaskedDaggerBuffer`` and the two learners'
+  ``action_masks=True``: the same with invalid-action masking (DESIGN.md
+  10.9).  The collector samples from the allowed actions only, so a rollout
+  never bumps at any beta; the learners' softmax runs over each sample's mask
+  with the label (and, under PPO, the taken action) added -- the planner never
+  labels an action the mask forbids, so the label is always in the support.
 
 The policy module is the one ``PPOLearner``, ``save_checkpoint`` and
 ``evaluate_policy`` take: a warm start followed by ``ppo.learn`` needs no
@@ -38,7 +44,7 @@ import torch
 import torch.nn.functional as Fn
 
 from . import _native, learn_ops
-from .collector import RolloutBuffer, RolloutCollector, _p
+from .collector import MaskedRolloutBuffer, RolloutBuffer, RolloutCollector, _p
 from .env import BatchedGridEnv, FrontierDists
 from .planner import FrontierExplorer
 from .ppo import PPOLearner, run_loop
@@ -75,6 +81,14 @@ class DaggerBuffer(RolloutBuffer):
     policy_actions: Optional[torch.Tensor] = None
     expert_dists: Optional[torch.Tensor] = None
     expert_set: Optional[torch.Tensor] = None
+
+
+@dataclass
+class MaskedDaggerBuffer(DaggerBuffer, MaskedRolloutBuffer):
+    """A ``DaggerBuffer`` of a ``MaskedDaggerCollector``: ``action_masks`` uint8
+    [T, N] as ``MaskedRolloutBuffer``'s.  ``actions``, ``policy_actions``, every
+    labelled ``expert_actions`` and ``expert_set`` lie inside the masks.  Taken
+    wherever a ``MaskedRolloutBuffer`` or a ``DaggerBuffer`` is."""
 
 
 def _check_labels(labels) -> str:
@@ -122,13 +136,15 @@ class DaggerCollector(RolloutCollector):
     ``expert_set`` as well.  The executed action does not change: the
     planner's lowest-k action with probability ``beta``."""
 
+    _masked = False      # MaskedDaggerCollector: the parent collector's masked path
+
     def __init__(self, env: BatchedGridEnv, policy, *args, expert: Optional[FrontierExplorer] = None,
                  beta: float = 1.0, mix_seed: int = 4242, labels: str = "action", **kwargs):
         if env.variant != _native.VN_VARIANT_CUBIC:
             raise ValueError("DaggerCollector: the frontier planner needs the CubicEnv variant")
-        if kwargs.get("action_masks"):
-            raise ValueError("DaggerCollector: action_masks is not supported (masked DAgger / kickstart: use "
-                             "RolloutCollector and PPOLearner)")
+        if kwargs.pop("action_masks", False):
+            raise ValueError("DaggerCollector takes no action_masks: masked DAgger / kickstart is "
+                             "MaskedDaggerCollector")
         info = env.info
         if info.pad_w > PLANNER_MAX_PAD or info.pad_d > PLANNER_MAX_PAD:
             raise ValueError(f"DaggerCollector: the frontier planner takes padded rooms of at most {PLANNER_MAX_PAD} x "
@@ -137,7 +153,7 @@ class DaggerCollector(RolloutCollector):
         self.beta = _check_beta(beta)
         self.mix_seed = int(mix_seed)
         self.labels = _check_labels(labels)
-        super().__init__(env, policy, *args, **kwargs)
+        super().__init__(env, policy, *args, action_masks=self._masked, **kwargs)
         T, N, dev = self.n_steps, self.N, self.device
         self.expert_actions = torch.zeros((T, N), dtype=torch.int32, device=dev)
         self.expert_dist = torch.full((T, N), -1, dtype=torch.int32, device=dev)
@@ -172,11 +188,78 @@ class DaggerCollector(RolloutCollector):
         """One rollout of n_steps.  The returned buffer views the collector's
         storage: it stays valid until the next ``collect()``."""
         rb = super().collect()
-        return DaggerBuffer(**{k: getattr(rb, k) for k in rb.__dataclass_fields__},
-                            expert_actions=self.expert_actions, expert_dist=self.expert_dist,
-                            label_weight=self.label_weight, took_expert=self.took_expert,
-                            policy_actions=self.policy_actions, expert_dists=self.expert_dists,
-                            expert_set=self.expert_set)
+        cls = MaskedDaggerBuffer if self._masked else DaggerBuffer     # (rb carries action_masks when masked)
+        return cls(**{k: getattr(rb, k) for k in rb.__dataclass_fields__},
+                   expert_actions=self.expert_actions, expert_dist=self.expert_dist,
+                   label_weight=self.label_weight, took_expert=self.took_expert,
+                   policy_actions=self.policy_actions, expert_dists=self.expert_dists,
+                   expert_set=self.expert_set)
+
+
+class MaskedDaggerCollector(DaggerCollector):
+    """A ``DaggerCollector`` with invalid-action masking: the
+    parent ``RolloutCollector``'s masked path -- per step ``vn_action_mask`` on
+    the observation into row t of the [T, N] mask buffer, the layer kernels and
+    ``vn_policy_head_masked`` -- then the unchanged planner labels and
+    ``vn_dagger_mix``.  The planner's action is always inside the mask (both
+    read an in-bounds neighbour with belief >= 0), so no executed action bumps
+    at any ``beta``.  ``collect()`` returns a ``MaskedDaggerBuffer``; ``act()``
+    and ``set_beta`` are as inherited.  Takes no ``action_masks`` keyword; f32
+    collectors on a CubicEnv only, rooms within the planner's bound."""
+
+    _masked = True
+
+    def __init__(self, env: BatchedGridEnv, policy, *args, **kwargs):
+        if "action_masks" in kwargs:
+            raise TypeError("MaskedDaggerCollector takes no action_masks keyword (it always masks)")
+        super().__init__(env, policy, *args, **kwargs)
+
+
+def _allowed(masks: torch.Tensor, A: int, always: torch.Tensor) -> torch.Tensor:
+    """S [M, A] bool: the mask's bits below A with ``always`` (the label's bits of a labelled
+    sample, the taken action) added; an empty row counts as full (include/voxnav.h
+    vn_bc_loss_masked)."""
+    ar = torch.arange(A, device=masks.device)
+    S = ((masks.view(-1, 1).to(torch.int64) >> ar) & 1).bool() | always
+    return S | ~S.any(-1, keepdim=True)
+
+
+def _cross_entropy(logits: torch.Tensor, labels: torch.Tensor, w: torch.Tensor, sets: bool,
+                   masks: Optional[torch.Tensor] = None, taken: Optional[torch.Tensor] = None):
+    """The torch path's cross-entropy of both learners, on the minibatch's rows.  ``labels``: the
+    expert's actions, or (``sets``) their uint8 sets; ``w`` [M]: 1 where the weight labels the
+    sample; ``masks`` (uint8 [M], or None): the softmax runs over S = mask | label bits of a
+    labelled sample | ``taken`` (the executed actions, int64, under PPO), an empty S as full.
+    -> (logits with -inf outside S, log_softmax with zeros outside S, the label's (the set's)
+    log-probability [M], w with empty sets dropped, right_of(argmax) -> the argmax is the label's)."""
+    A = logits.shape[-1]
+    ar = torch.arange(A, device=logits.device)
+    if sets:
+        # in_set [M, A]: bit j of the sample's set; -log sum_{j in set} p_j = lse(z) - lse(z over the set)
+        in_set = ((labels.long().view(-1, 1) >> ar) & 1).bool()
+        some = in_set.any(-1)
+        w = w * some.to(w.dtype)
+    else:
+        lab = labels.long()
+    S = None
+    if masks is not None:
+        always = (in_set if sets else ar.view(1, A) == lab.view(-1, 1)) & (w != 0).view(-1, 1)
+        if taken is not None:
+            always = always | (ar.view(1, A) == taken.view(-1, 1))
+        S = _allowed(masks, A, always)
+        logits = logits.masked_fill(~S, float("-inf"))
+    lp_all = torch.log_softmax(logits, dim=-1)
+    if S is not None:
+        # a masked action's terms are zeros (exp(0) 0 in the entropy), and it gets no gradient
+        lp_all = torch.where(S, lp_all, lp_all.new_zeros(()))
+    if sets:
+        sel = in_set if S is None else in_set & S          # (a labelled sample's set lies in S)
+        masked = logits.masked_fill(~sel, float("-inf"))
+        masked = torch.where(sel.any(-1, keepdim=True), masked, torch.zeros_like(masked))   # (empty: no -inf row)
+        lp = torch.logsumexp(masked, dim=-1) - torch.logsumexp(logits, dim=-1)
+        return logits, lp_all, lp, w, lambda amax: in_set.gather(1, amax.view(-1, 1)).flatten()
+    lp = lp_all.gather(1, lab.view(-1, 1)).flatten()
+    return logits, lp_all, lp, w, lambda amax: amax == lab
 
 
 class BCLearner(PPOLearner):
@@ -193,15 +276,24 @@ class BCLearner(PPOLearner):
     probability of the whole set of equally short actions (the formula of
     vn_bc_loss_set, through ``learn_ops.bc_loss_set`` on the GPU), a sample
     with an empty set is unlabelled, and ``accuracy`` counts the argmax lying
-    in the set."""
+    in the set.
+
+    ``action_masks=True`` trains on a ``MaskedDaggerBuffer``: every sample's
+    softmax, entropy and argmax run over S = its mask with the label's bits
+    (of a labelled sample) added, an empty set counting as full (the rule of
+    vn_bc_loss_masked), in ``learn_ops.bc_loss_masked`` / ``bc_loss_set_masked``
+    where the fused loss runs, else through torch autograd of the same formula
+    (``PPOLearner._heads``' masked_fill / log_softmax / where)."""
 
     def __init__(self, policy, learning_rate: float = 3e-4, n_epochs: int = 10, batch_size: int = 64,
                  ent_coef: float = 0.0, vf_coef: float = 0.5, max_grad_norm: float = 0.5, seed: int = 0,
-                 process_group=None, labels: str = "action"):
+                 process_group=None, labels: str = "action", action_masks: bool = False):
         super().__init__(policy, learning_rate=learning_rate, n_epochs=n_epochs, batch_size=batch_size,
                          ent_coef=ent_coef, vf_coef=vf_coef, max_grad_norm=max_grad_norm, seed=seed,
-                         process_group=process_group)
-        self.fused_updates = 0     # minibatches that went through learn_ops.bc_loss / bc_loss_set
+                         process_group=process_group, action_masks=action_masks)
+        # minibatches that went through learn_ops.bc_loss / bc_loss_set or, counted in
+        # masked_fused_updates as well, their masked forms
+        self.fused_updates = 0
         self.labels = _check_labels(labels)
 
     def _labels(self, buf):
@@ -212,6 +304,7 @@ class BCLearner(PPOLearner):
         (all-reduce), clip, Adam.  Returns the logged values as a device
         tensor: cross-entropy, value loss, entropy loss, loss, accuracy,
         labelled share, grad norm."""
+        self._check_masks(buf)
         if self.recurrent:
             (lat_pi, lat_vf, lat_pair), src = self._evaluate_recurrent(buf, packed or self._pack_begin(buf, idx))
         else:
@@ -234,18 +327,8 @@ class BCLearner(PPOLearner):
         A = logits.shape[-1]
         w = torch.ones_like(values) if weight is None else (weight[src] != 0).to(values.dtype)
         ret = buf.returns.reshape(-1)[src]
-        lp_all = torch.log_softmax(logits, dim=-1)
-        if self.labels == "set":
-            # in_set [M, A]: bit j of the sample's set; -log sum_{j in S} p_j = lse(z) - lse(z over S)
-            in_set = ((labels[src].long().view(-1, 1) >> torch.arange(A, device=logits.device)) & 1).bool()
-            some = in_set.any(-1)
-            w = w * some.to(w.dtype)
-            masked = logits.masked_fill(~in_set, float("-inf"))
-            masked = torch.where(some.view(-1, 1), masked, torch.zeros_like(masked))   # (an empty set: no -inf row)
-            lp = torch.logsumexp(masked, dim=-1) - torch.logsumexp(logits, dim=-1)
-        else:
-            lab = labels[src].long()
-            lp = lp_all.gather(1, lab.view(-1, 1)).flatten()
+        masks = buf.action_masks.reshape(-1)[src] if self.action_masks else None
+        logits, lp_all, lp, w, right_of = _cross_entropy(logits, labels[src], w, self.labels == "set", masks)
         entropy = -(lp_all.exp() * lp_all).sum(-1)
         n = w.sum()
         den = torch.clamp(n, min=1.0)
@@ -263,8 +346,7 @@ class BCLearner(PPOLearner):
             ar = torch.arange(A, device=logits.device).expand_as(logits)
             amax = torch.where(logits == top, ar, torch.full_like(ar, A)).min(-1).values   # ties: the lowest index
             # counts are integers: their quotients in f64, as the kernel's
-            right = in_set.gather(1, amax.view(-1, 1)).flatten() if self.labels == "set" else amax == lab
-            acc = (w.double() * right.double()).sum() / den.double()
+            acc = (w.double() * right_of(amax).double()).sum() / den.double()
             return torch.stack([bc.detach().double(), value_loss.detach().double(), entropy_loss.detach().double(),
                                 loss.detach().double(), acc, n.double() / w.numel(), gnorm.detach().double()])
 
@@ -274,9 +356,16 @@ class BCLearner(PPOLearner):
         and its gradient in the fused kernel (learn_ops.bc_loss / bc_loss_set),
         then ``PPOLearner._step_fused``."""
         pol = self.policy
-        fused = learn_ops.bc_loss_set if self.labels == "set" else learn_ops.bc_loss
-        dh, grads, stats = fused(h, pol.action_net, pol.value_net, src, labels, weight, buf.returns.reshape(-1),
-                                 self.ent_coef, self.vf_coef)
+        if self.action_masks:
+            fused = learn_ops.bc_loss_set_masked if self.labels == "set" else learn_ops.bc_loss_masked
+            dh, grads, stats = fused(h, pol.action_net, pol.value_net, src, labels, weight,
+                                     buf.action_masks.reshape(-1), buf.returns.reshape(-1), self.ent_coef,
+                                     self.vf_coef)
+            self.masked_fused_updates += 1
+        else:
+            fused = learn_ops.bc_loss_set if self.labels == "set" else learn_ops.bc_loss
+            dh, grads, stats = fused(h, pol.action_net, pol.value_net, src, labels, weight, buf.returns.reshape(-1),
+                                     self.ent_coef, self.vf_coef)
         self.fused_updates += 1
         return self._step_fused(h, dh, grads, stats)
 
@@ -286,6 +375,7 @@ class BCLearner(PPOLearner):
         labelled samples), ``value_loss``, ``entropy_loss``, ``loss``,
         ``accuracy`` (labelled samples whose argmax is the label), ``labelled``
         (their share), ``grad_norm``, and ``n_minibatches``, ``n_updates``."""
+        self._check_masks(buf)
         self._labels(buf)
         m, n_mb = self._run_epochs(buf, epoch_orders)
         return dict(bc_loss=m[0], value_loss=m[1], entropy_loss=m[2], loss=m[3], accuracy=m[4], labelled=m[5],
@@ -334,16 +424,26 @@ class KickstartLearner(PPOLearner):
     executed planner action the importance ratio would pair an action with
     another action's old log-prob (``DaggerBuffer``).  ``labels`` as
     ``BCLearner``'s.  With a process group the ranks' gradients are averaged
-    equally, although their labelled counts may differ."""
+    equally, although their labelled counts may differ.
+
+    ``action_masks=True`` trains on a ``MaskedDaggerBuffer`` (beta = 0): every
+    sample's softmax runs over S = its mask with the taken action and the
+    label's bits (of a labelled sample) added, an empty set counting as full
+    (the rule of vn_ppo_bc_loss_masked), in ``learn_ops.ppo_bc_loss_masked`` /
+    ``ppo_bc_loss_set_masked`` where the fused loss runs, else through torch
+    autograd of the same formula."""
 
     def __init__(self, policy, learning_rate: float = 3e-4, n_epochs: int = 10, batch_size: int = 64,
                  clip_range: float = 0.2, ent_coef: float = 0.01, vf_coef: float = 0.5, max_grad_norm: float = 0.5,
                  normalize_advantage: bool = True, seed: int = 0, process_group=None, bc_coef: float = 1.0,
-                 labels: str = "action"):
+                 labels: str = "action", action_masks: bool = False):
         super().__init__(policy, learning_rate=learning_rate, n_epochs=n_epochs, batch_size=batch_size,
                          clip_range=clip_range, ent_coef=ent_coef, vf_coef=vf_coef, max_grad_norm=max_grad_norm,
-                         normalize_advantage=normalize_advantage, seed=seed, process_group=process_group)
-        self.fused_updates = 0     # minibatches that went through learn_ops.ppo_bc_loss / ppo_bc_loss_set
+                         normalize_advantage=normalize_advantage, seed=seed, process_group=process_group,
+                         action_masks=action_masks)
+        # minibatches that went through learn_ops.ppo_bc_loss / ppo_bc_loss_set or, counted in
+        # masked_fused_updates as well, their masked forms
+        self.fused_updates = 0
         self.labels = _check_labels(labels)
         self.bc_coef = _check_bc_coef(bc_coef)
 
@@ -359,6 +459,7 @@ class KickstartLearner(PPOLearner):
         values as a device tensor: ``PPOLearner.update``'s six (the loss with
         the cross-entropy term), cross-entropy, accuracy, labelled share, grad
         norm."""
+        self._check_masks(buf)
         if self.recurrent:
             (lat_pi, lat_vf, lat_pair), src = self._evaluate_recurrent(buf, packed or self._pack_begin(buf, idx))
         else:
@@ -373,11 +474,18 @@ class KickstartLearner(PPOLearner):
                 h = learn_ops.mlp_pair(ex.policy_net, ex.value_net, lat_pi, None if lat_vf is lat_pi else lat_vf,
                                        x_pair=lat_pair, stacked=True)
                 if h is not None:
-                    fused = learn_ops.ppo_bc_loss_set if self.labels == "set" else learn_ops.ppo_bc_loss
-                    dh, grads, stats = fused(h, pol.action_net, pol.value_net, src, buf.actions.reshape(-1),
-                                             buf.advantages.reshape(-1), buf.log_probs.reshape(-1),
-                                             buf.returns.reshape(-1), labels, weight, self.clip_range, self.ent_coef,
-                                             self.vf_coef, self.bc_coef, norm)
+                    bufs = (buf.actions.reshape(-1), buf.advantages.reshape(-1), buf.log_probs.reshape(-1),
+                            buf.returns.reshape(-1), labels, weight)
+                    coefs = (self.clip_range, self.ent_coef, self.vf_coef, self.bc_coef, norm)
+                    if self.action_masks:
+                        fused = (learn_ops.ppo_bc_loss_set_masked if self.labels == "set"
+                                 else learn_ops.ppo_bc_loss_masked)
+                        dh, grads, stats = fused(h, pol.action_net, pol.value_net, src, *bufs,
+                                                 buf.action_masks.reshape(-1), *coefs)
+                        self.masked_fused_updates += 1
+                    else:
+                        fused = learn_ops.ppo_bc_loss_set if self.labels == "set" else learn_ops.ppo_bc_loss
+                        dh, grads, stats = fused(h, pol.action_net, pol.value_net, src, *bufs, *coefs)
                     self.fused_updates += 1
                     return self._step_fused(h, dh, grads, stats)
         # torch's ops and autograd: the CPU path, and heads the fused kernel does not take
@@ -386,8 +494,11 @@ class KickstartLearner(PPOLearner):
         logits = learn_ops.linear(h_pi, pol.action_net)
         values = learn_ops.linear(h_vf, pol.value_net).flatten()
         A = logits.shape[-1]
-        lp_all = torch.log_softmax(logits, dim=-1)
-        log_prob = lp_all.gather(1, buf.actions.reshape(-1)[src].long().view(-1, 1)).flatten()
+        taken = buf.actions.reshape(-1)[src].long()
+        w = torch.ones_like(values) if weight is None else (weight[src] != 0).to(values.dtype)
+        masks = buf.action_masks.reshape(-1)[src] if self.action_masks else None
+        logits, lp_all, lp, w, right_of = _cross_entropy(logits, labels[src], w, self.labels == "set", masks, taken)
+        log_prob = lp_all.gather(1, taken.view(-1, 1)).flatten()
         entropy = -(lp_all.exp() * lp_all).sum(-1)
         adv = buf.advantages.reshape(-1)[src]
         if norm:
@@ -398,17 +509,6 @@ class KickstartLearner(PPOLearner):
         policy_loss = -torch.min(adv * ratio, adv * torch.clamp(ratio, 1 - self.clip_range, 1 + self.clip_range)).mean()
         value_loss = Fn.mse_loss(ret, values)
         entropy_loss = -entropy.mean()
-        w = torch.ones_like(values) if weight is None else (weight[src] != 0).to(values.dtype)
-        if self.labels == "set":
-            in_set = ((labels[src].long().view(-1, 1) >> torch.arange(A, device=logits.device)) & 1).bool()
-            some = in_set.any(-1)
-            w = w * some.to(w.dtype)
-            masked = logits.masked_fill(~in_set, float("-inf"))
-            masked = torch.where(some.view(-1, 1), masked, torch.zeros_like(masked))   # (an empty set: no -inf row)
-            lp = torch.logsumexp(masked, dim=-1) - torch.logsumexp(logits, dim=-1)
-        else:
-            lab = labels[src].long()
-            lp = lp_all.gather(1, lab.view(-1, 1)).flatten()
         n = w.sum()
         den = torch.clamp(n, min=1.0)
         bc = (w * -lp).sum() / den
@@ -423,8 +523,7 @@ class KickstartLearner(PPOLearner):
             top = logits.max(-1, keepdim=True).values
             ar = torch.arange(A, device=logits.device).expand_as(logits)
             amax = torch.where(logits == top, ar, torch.full_like(ar, A)).min(-1).values   # ties: the lowest index
-            right = in_set.gather(1, amax.view(-1, 1)).flatten() if self.labels == "set" else amax == lab
-            acc = (w.double() * right.double()).sum() / den.double()
+            acc = (w.double() * right_of(amax).double()).sum() / den.double()
             return torch.stack([policy_loss.detach().double(), value_loss.detach().double(),
                                 entropy_loss.detach().double(), loss.detach().double(),
                                 ((torch.exp(log_ratio) - 1) - log_ratio).mean().double(),
@@ -435,6 +534,7 @@ class KickstartLearner(PPOLearner):
         """One ``train()`` over a ``DaggerBuffer`` collected with beta = 0
         (n_epochs passes).  Returns ``PPOLearner.train``'s keys plus
         ``bc_loss``, ``accuracy`` and ``labelled`` (``BCLearner.train``)."""
+        self._check_masks(buf)
         self._labels(buf)
         took = getattr(buf, "took_expert", None)
         if took is not None and bool(took.any()):       # one host read per rollout

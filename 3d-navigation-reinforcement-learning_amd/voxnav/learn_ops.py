@@ -327,12 +327,53 @@ def bc_loss_set(h: torch.Tensor, action_net: torch.nn.Linear, value_net: torch.n
                       "uint8 label sets / uint8 weights / f32 returns", (float(ent_coef), float(vf_coef)))
 
 
+def _required_masks(name: str, action_masks) -> None:
+    """The masked entry points take no absent mask buffer (NULL is refused like any required pointer)."""
+    if action_masks is None:
+        raise ValueError(f"{name}: action_masks is required (uint8 masks)")
+
+
+def bc_loss_masked(h: torch.Tensor, action_net: torch.nn.Linear, value_net: torch.nn.Linear,
+                   src: Optional[torch.Tensor], labels: torch.Tensor, weight: Optional[torch.Tensor],
+                   action_masks: torch.Tensor, returns: torch.Tensor, ent_coef: float, vf_coef: float):
+    """``bc_loss`` with invalid-action masking (csrc/voxnav_masked_bc_loss.hip, the
+    rule in include/voxnav.h vn_bc_loss_masked): ``action_masks`` uint8, a flat
+    rollout buffer like the others, bit j set where action j was allowed; each
+    sample's softmax, entropy and argmax run over its mask with the label (of a
+    labelled sample) added, an empty set counting as full, and the logits of
+    the other actions get a gradient of exactly 0.  Arguments, outputs and
+    stats as ``bc_loss``."""
+    _required_masks("bc_loss_masked", action_masks)
+    return _head_loss("bc_loss_masked", h, action_net, value_net, src,
+                      ((labels, torch.int32), (weight, torch.uint8), (action_masks, torch.uint8),
+                       (returns, torch.float32)),
+                      "int32 labels / uint8 weights / uint8 masks / f32 returns", (float(ent_coef), float(vf_coef)))
+
+
+def bc_loss_set_masked(h: torch.Tensor, action_net: torch.nn.Linear, value_net: torch.nn.Linear,
+                       src: Optional[torch.Tensor], label_set: torch.Tensor, weight: Optional[torch.Tensor],
+                       action_masks: torch.Tensor, returns: torch.Tensor, ent_coef: float, vf_coef: float):
+    """``bc_loss_set`` with invalid-action masking (``vn_bc_loss_set_masked``):
+    ``bc_loss_masked`` with the labelled sample's whole set added to its
+    allowed actions."""
+    _required_masks("bc_loss_set_masked", action_masks)
+    return _head_loss("bc_loss_set_masked", h, action_net, value_net, src,
+                      ((label_set, torch.uint8), (weight, torch.uint8), (action_masks, torch.uint8),
+                       (returns, torch.float32)),
+                      "uint8 label sets / uint8 weights / uint8 masks / f32 returns",
+                      (float(ent_coef), float(vf_coef)))
+
+
 def _ppo_bc(name, h, action_net, value_net, src, actions, advantages, old_log_prob, returns, labels, label_dtype,
-            weight, clip_range, ent_coef, vf_coef, bc_coef, normalize_advantage):
+            weight, clip_range, ent_coef, vf_coef, bc_coef, normalize_advantage, action_masks=None):
+    masked = name.endswith("_masked")
+    if masked:
+        _required_masks(name, action_masks)
     return _head_loss(name, h, action_net, value_net, src,
                       ((actions, torch.int32), (advantages, torch.float32), (old_log_prob, torch.float32),
-                       (returns, torch.float32), (labels, label_dtype), (weight, torch.uint8)),
-                      "int32 actions / f32 values / labels / uint8 weights",
+                       (returns, torch.float32), (labels, label_dtype), (weight, torch.uint8),
+                       *(((action_masks, torch.uint8),) if masked else ())),
+                      "int32 actions / f32 values / labels / uint8 weights" + (" / uint8 masks" if masked else ""),
                       (float(clip_range), float(ent_coef), float(vf_coef), float(bc_coef),
                        int(bool(normalize_advantage))), adv_words=128, n_stats=9)
 
@@ -362,6 +403,35 @@ def ppo_bc_loss_set(h: torch.Tensor, action_net: torch.nn.Linear, value_net: tor
     unlabelled, accuracy counts the argmax lying in the set."""
     return _ppo_bc("ppo_bc_loss_set", h, action_net, value_net, src, actions, advantages, old_log_prob, returns,
                    label_set, torch.uint8, weight, clip_range, ent_coef, vf_coef, bc_coef, normalize_advantage)
+
+
+def ppo_bc_loss_masked(h: torch.Tensor, action_net: torch.nn.Linear, value_net: torch.nn.Linear,
+                       src: Optional[torch.Tensor], actions: torch.Tensor, advantages: torch.Tensor,
+                       old_log_prob: torch.Tensor, returns: torch.Tensor, labels: torch.Tensor,
+                       weight: Optional[torch.Tensor], action_masks: torch.Tensor, clip_range: float, ent_coef: float,
+                       vf_coef: float, bc_coef: float, normalize_advantage: bool):
+    """``ppo_bc_loss`` with invalid-action masking
+    (csrc/voxnav_masked_ppo_bc_loss.hip, the rule in include/voxnav.h
+    vn_ppo_bc_loss_masked): ``action_masks`` uint8 as ``ppo_loss_masked``'s;
+    each sample's softmax, log-prob, entropy and argmax run over its mask with
+    the taken action and the label (of a labelled sample) added, an empty set
+    counting as full.  Arguments, outputs and stats as ``ppo_bc_loss``."""
+    return _ppo_bc("ppo_bc_loss_masked", h, action_net, value_net, src, actions, advantages, old_log_prob, returns,
+                   labels, torch.int32, weight, clip_range, ent_coef, vf_coef, bc_coef, normalize_advantage,
+                   action_masks)
+
+
+def ppo_bc_loss_set_masked(h: torch.Tensor, action_net: torch.nn.Linear, value_net: torch.nn.Linear,
+                           src: Optional[torch.Tensor], actions: torch.Tensor, advantages: torch.Tensor,
+                           old_log_prob: torch.Tensor, returns: torch.Tensor, label_set: torch.Tensor,
+                           weight: Optional[torch.Tensor], action_masks: torch.Tensor, clip_range: float,
+                           ent_coef: float, vf_coef: float, bc_coef: float, normalize_advantage: bool):
+    """``ppo_bc_loss_set`` with invalid-action masking
+    (``vn_ppo_bc_loss_set_masked``): ``ppo_bc_loss_masked`` with the labelled
+    sample's whole set added to its allowed actions."""
+    return _ppo_bc("ppo_bc_loss_set_masked", h, action_net, value_net, src, actions, advantages, old_log_prob,
+                   returns, label_set, torch.uint8, weight, clip_range, ent_coef, vf_coef, bc_coef,
+                   normalize_advantage, action_masks)
 
 
 def grad_norm_scale(params, max_norm: float, work: Optional[torch.Tensor] = None):

@@ -82,7 +82,8 @@ class PPOLearner:
         self.max_grad_norm = float(max_grad_norm)
         self.normalize_advantage = bool(normalize_advantage)
         self.action_masks = bool(action_masks)
-        self.masked_fused_updates = 0   # minibatches that went through learn_ops.ppo_loss_masked
+        # minibatches that went through learn_ops.ppo_loss_masked (imitate's learners: their masked losses)
+        self.masked_fused_updates = 0
         self.rng = np.random.default_rng(seed)
         self.group = process_group
         self.params = [p for p in policy.parameters() if p.requires_grad]

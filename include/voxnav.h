@@ -1105,6 +1105,59 @@ int vn_ppo_bc_loss_set(const float *hp, const float *hv, int64_t ldh, const floa
                        float *dhp, float *dhv, float *grad_heads, double *stats, double *adv_sums, float *part,
                        double *spart, void *stream);
 
+/* vn_bc_loss / vn_bc_loss_set / vn_ppo_bc_loss / vn_ppo_bc_loss_set with
+ * invalid-action masking (csrc/voxnav_masked_bc_loss.hip,
+ * csrc/voxnav_masked_ppo_bc_loss.hip; masked DAgger and masked kickstart): each
+ * is its unmasked namesake with one more gathered buffer after weight, mask
+ * uint8, indexed by src like the others, bit j set where action j was allowed
+ * (vn_action_mask of the sample's observation).  With full = 2^A - 1 and L_i
+ * the label's bits where sample i is labelled (its weight nonzero or absent;
+ * labels: bit labels_i when 0 <= labels_i < A; label_set: label_set_i & full,
+ * labelled only when that is non-empty), else 0, the softmax of sample i runs
+ * over
+ *   S_i = (mask_i & full) | L_i                 (vn_bc_loss_masked, vn_bc_loss_set_masked)
+ *   S_i = (mask_i & full) | (1 << a_i) | L_i    (vn_ppo_bc_loss_masked, vn_ppo_bc_loss_set_masked)
+ * with an empty S_i counting as full -- vn_ppo_loss_masked's rule extended by
+ * the label, so neither the cross-entropy nor the ratio reads a log-probability
+ * outside the support:
+ *   lp_ij, p_ij, H_i as vn_ppo_loss_masked's over S_i; the argmax behind the accuracy runs over S_i
+ *   q_i   = one-hot at the label, or the softmax of z_i restricted to label_set_i & full, as unmasked
+ *   dz_ij = (the ppo term, where there is one, + the bc term) + the entropy term   (j in S_i),
+ *           exactly 0 otherwise
+ * Everything else is the unmasked entry's: n, bc_coef on the gradient scale,
+ * the value term, stats [6] / [9], grad_heads, the launches, the workspaces
+ * (sizes from vn_bc_loss_part_floats / vn_ppo_bc_loss_part_floats) and the
+ * refusals, plus a NULL mask.  With every S_i full the outputs are the unmasked
+ * entry's bits.  vn_ppo_bc_loss[_set]_masked with bc_coef = 0 and the labels
+ * inside the masks gives vn_ppo_loss_masked's dhp, dhv, grad_heads and
+ * stats[0..5] as values; with all advantages 0, normalize_advantage = 0,
+ * bc_coef = 1 and the taken actions inside the masks its gradients equal
+ * vn_bc_loss[_set]_masked's. */
+int vn_bc_loss_masked(const float *hp, const float *hv, int64_t ldh, const float *wa, const float *ba,
+                      const float *wv, const float *bv, const int64_t *src, const int32_t *labels,
+                      const uint8_t *weight, const uint8_t *mask, const float *returns, int32_t M, int32_t F,
+                      int32_t A, float ent_coef, float vf_coef, float *dhp, float *dhv, float *grad_heads,
+                      double *stats, float *part, double *spart, void *stream);
+int vn_bc_loss_set_masked(const float *hp, const float *hv, int64_t ldh, const float *wa, const float *ba,
+                          const float *wv, const float *bv, const int64_t *src, const uint8_t *label_set,
+                          const uint8_t *weight, const uint8_t *mask, const float *returns, int32_t M, int32_t F,
+                          int32_t A, float ent_coef, float vf_coef, float *dhp, float *dhv, float *grad_heads,
+                          double *stats, float *part, double *spart, void *stream);
+int vn_ppo_bc_loss_masked(const float *hp, const float *hv, int64_t ldh, const float *wa, const float *ba,
+                          const float *wv, const float *bv, const int64_t *src, const int32_t *actions,
+                          const float *advantages, const float *old_log_prob, const float *returns,
+                          const int32_t *labels, const uint8_t *weight, const uint8_t *mask, int32_t M, int32_t F,
+                          int32_t A, float clip_range, float ent_coef, float vf_coef, float bc_coef,
+                          int32_t normalize_advantage, float *dhp, float *dhv, float *grad_heads, double *stats,
+                          double *adv_sums, float *part, double *spart, void *stream);
+int vn_ppo_bc_loss_set_masked(const float *hp, const float *hv, int64_t ldh, const float *wa, const float *ba,
+                              const float *wv, const float *bv, const int64_t *src, const int32_t *actions,
+                              const float *advantages, const float *old_log_prob, const float *returns,
+                              const uint8_t *label_set, const uint8_t *weight, const uint8_t *mask, int32_t M,
+                              int32_t F, int32_t A, float clip_range, float ent_coef, float vf_coef, float bc_coef,
+                              int32_t normalize_advantage, float *dhp, float *dhv, float *grad_heads, double *stats,
+                              double *adv_sums, float *part, double *spart, void *stream);
+
 /* DAgger's executed action for one collector step (csrc/voxnav_bc_loss.hip):
  * per agent i of N, with the planner's proposal expert[i] / dist[i]
  * (vn_plan_frontier) and the policy's own sample policy[i],

@@ -7,7 +7,12 @@ loss    vn_ppo_loss_masked against vn_ppo_loss (csrc/voxnav_masked_loss.hip, csr
         the method of scripts/bc_loss_bench.py (HIP events around --batch calls back to back, median of
         --reps repetitions after --warmup, the case list --rounds times in turn).  The masks are random
         with the taken action allowed (about half of the other actions forbidden); ``full`` is the
-        masked kernel under all-allowed masks.
+        masked kernel under all-allowed masks.  Likewise the four masked cross-entropy
+        entry points against their unmasked counterparts -- vn_bc_loss[_set]_masked
+        (csrc/voxnav_masked_bc_loss.hip) and vn_ppo_bc_loss[_set]_masked
+        (csrc/voxnav_masked_ppo_bc_loss.hip), bc_coef 0.7 -- with labels inside the same masks (the
+        set form: the mask's bits drawn with probability 1/2, never empty), about a fifth of the weights
+        zero; ``ratio_to_unmasked`` and, per round, ``rounds_ratio_to_unmasked``.
 collect the C3 (PPO-MLP, P2_training) and C4 (PPO-LSTM f32, P3_training) collectors of bench.py at
         --agents agents, --T steps: ``action_masks`` off (the fused vn_mlp_head_f32), on (vn_action_mask
         + vn_linear_f32 per layer + vn_policy_head_masked), and off with the fused head disabled too
@@ -30,6 +35,7 @@ sys.path.insert(0, str(REPO / "scripts"))
 import torch  # noqa: E402
 
 from bc_loss_bench import timed  # noqa: E402
+from voxnav import learn_ops  # noqa: E402
 from voxnav.learn_ops import ppo_loss, ppo_loss_masked  # noqa: E402
 
 
@@ -42,6 +48,11 @@ def loss_leg(args, dev):
     adv, olp, ret = torch.randn(R, device=dev), torch.randn(R, device=dev) - 1.8, torch.randn(R, device=dev)
     masks = ((1 << act) | torch.randint(0, 1 << A, (R,), device=dev)).to(torch.uint8)
     full = torch.full((R,), (1 << A) - 1, dtype=torch.uint8, device=dev)
+    # the planner's labels lie inside the mask: one allowed action, a non-empty subset
+    lab = torch.multinomial(((masks.view(-1, 1).long() >> torch.arange(A, device=dev)) & 1).float(), 1).flatten()
+    sets = ((masks.long() & torch.randint(0, 1 << A, (R,), device=dev)) | (1 << lab)).to(torch.uint8)
+    lab = lab.to(torch.int32)
+    wgt = (torch.rand(R, device=dev) >= 0.2).to(torch.uint8)
     out = {}
     for F in args.widths:
         an, vn = torch.nn.Linear(F, A).to(dev), torch.nn.Linear(F, 1).to(dev)
@@ -52,6 +63,19 @@ def loss_leg(args, dev):
             "ppo_loss_masked_full": lambda: ppo_loss_masked(h, an, vn, src, act, adv, olp, ret, full, 0.2, 0.01, 0.5,
                                                             True),
         }
+        pair = {}                                    # masked case -> its unmasked counterpart
+        for name, labels in (("bc_loss", lab), ("bc_loss_set", sets)):
+            f0, f1 = getattr(learn_ops, name), getattr(learn_ops, name + "_masked")
+            cases[name] = lambda f0=f0, labels=labels: f0(h, an, vn, src, labels, wgt, ret, 0.01, 0.5)
+            cases[name + "_masked"] = lambda f1=f1, labels=labels: f1(h, an, vn, src, labels, wgt, masks, ret, 0.01, 0.5)
+            pair[name + "_masked"] = name
+        for name, labels in (("ppo_bc_loss", lab), ("ppo_bc_loss_set", sets)):
+            f0, f1 = getattr(learn_ops, name), getattr(learn_ops, name + "_masked")
+            cases[name] = lambda f0=f0, labels=labels: f0(h, an, vn, src, act, adv, olp, ret, labels, wgt, 0.2, 0.01,
+                                                          0.5, 0.7, True)
+            cases[name + "_masked"] = lambda f1=f1, labels=labels: f1(h, an, vn, src, act, adv, olp, ret, labels, wgt,
+                                                                      masks, 0.2, 0.01, 0.5, 0.7, True)
+            pair[name + "_masked"] = name
         rounds = [{k: timed(fn, args.reps, args.warmup, dev, args.batch) for k, fn in cases.items()}
                   for _ in range(args.rounds)]
         r = rounds[0]
@@ -60,6 +84,11 @@ def loss_leg(args, dev):
             r[k]["rounds_median_ms"] = med
             r[k]["ratio_to_ppo_loss"] = round(statistics.median(med) /
                                               statistics.median([x["ppo_loss"]["median_ms"] for x in rounds]), 4)
+        for k, base in pair.items():
+            per = [round(x[k]["median_ms"] / x[base]["median_ms"], 4) for x in rounds]
+            r[k]["rounds_ratio_to_unmasked"] = per
+            r[k]["ratio_to_unmasked"] = round(statistics.median([x[k]["median_ms"] for x in rounds]) /
+                                              statistics.median([x[base]["median_ms"] for x in rounds]), 4)
         out[str(F)] = r
     return out
 

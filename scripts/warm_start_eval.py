@@ -15,7 +15,11 @@ plain ``ppo.learn``, or ``imitate.kickstart`` with bc_coef = --bc-decay ^ iterat
 table row for the policy after them.  --action-masks (with --then ppo): the then-phase
 collects with invalid-action masking -- a ``RolloutCollector(action_masks=True)`` on the same env (the
 DAgger collector has no masks; it starts from a fresh reset), ``PPOLearner(action_masks=True)`` -- and
-its table row is evaluated with masks too.  Prints the per-iteration rows, the table and one JSON line.
+its table row is evaluated with masks too.  --action-masks with --then kickstart: masked
+DAgger and masked kickstart -- the warm start runs on a ``MaskedDaggerCollector`` with
+``BCLearner(action_masks=True)``, the then-phase continues on the same collector with
+``KickstartLearner(action_masks=True)``, and every evaluation of the policy is masked (the final weights are
+evaluated without masks as well).  Prints the per-iteration rows, the table and one JSON line.
 Needs a GPU."""
 import argparse
 import json
@@ -30,7 +34,8 @@ import torch  # noqa: E402
 from voxnav.collector import RolloutCollector  # noqa: E402
 from voxnav.env import BatchedGridEnv  # noqa: E402
 from voxnav.evaluate import RESULTS_HEADER, evaluate_policy, results_table_row  # noqa: E402
-from voxnav.imitate import BCLearner, DaggerCollector, KickstartLearner, kickstart, warm_start  # noqa: E402
+from voxnav.imitate import (BCLearner, DaggerCollector, KickstartLearner, MaskedDaggerCollector, kickstart,  # noqa: E402
+                            warm_start)
 from voxnav.normalize import RewardNormalizer  # noqa: E402
 from voxnav.planner import evaluate_planner  # noqa: E402
 from voxnav.ppo import PPOLearner, learn  # noqa: E402
@@ -64,10 +69,12 @@ def main():
     ap.add_argument("--then-iterations", type=int, default=8)
     ap.add_argument("--bc-decay", type=float, default=0.7, help="kickstart: bc_coef = bc_decay ^ iteration")
     ap.add_argument("--action-masks", action="store_true",
-                    help="--then ppo with invalid-action masking, evaluated with masks too (DESIGN.md 10.8)")
+                    help="--then ppo with invalid-action masking, evaluated with masks too (DESIGN.md 10.8); "
+                         "--then kickstart: masked DAgger and masked kickstart throughout (DESIGN.md 10.9)")
     args = ap.parse_args()
-    if args.action_masks and args.then != "ppo":
-        raise SystemExit("--action-masks goes with --then ppo")
+    if args.action_masks and args.then is None:
+        raise SystemExit("--action-masks goes with --then ppo or --then kickstart")
+    masked_imitation = args.action_masks and args.then == "kickstart"
     if not torch.cuda.is_available():
         raise SystemExit("warm_start_eval.py needs a GPU")
     dev = "cuda:0"
@@ -75,14 +82,17 @@ def main():
     pol = (RecurrentActorCriticPolicy() if args.policy == "lstm" else ActorCriticPolicy()).to(dev)
     eval_rooms = load_archive_set(args.eval_set)
     kw = dict(n_episodes=args.episodes, local_map_length=args.L, seed=args.seed, device=dev)
-    rows = {"untrained policy": evaluate_policy(pol, eval_rooms, **kw)}
+    ekw = dict(kw, action_masks=True) if masked_imitation else kw       # the policy's evaluations
+    how = ", masked evaluation" if masked_imitation else ""
+    rows = {"untrained policy" + how: evaluate_policy(pol, eval_rooms, **ekw)}
 
     env = BatchedGridEnv(num_agents=args.agents, rooms=load_archive_set(args.train_set), local_map_length=args.L,
                          device=dev)
     rnorm = RewardNormalizer(args.agents, 0.99, device=dev) if args.norm_reward else None
-    col = DaggerCollector(env, pol, n_steps=args.n_steps, labels=args.labels, reward_norm=rnorm)
+    col = (MaskedDaggerCollector if masked_imitation else DaggerCollector)(env, pol, n_steps=args.n_steps,
+                                                                           labels=args.labels, reward_norm=rnorm)
     ln = BCLearner(pol, learning_rate=args.lr, n_epochs=args.epochs, batch_size=args.batch, vf_coef=args.vf_coef,
-                   seed=args.seed, labels=args.labels)
+                   seed=args.seed, labels=args.labels, action_masks=masked_imitation)
     t0 = time.time()
 
     def show(it, done, st):
@@ -95,7 +105,8 @@ def main():
     torch.cuda.synchronize()
     train_s = time.time() - t0
     tag = (" (set labels)" if args.labels == "set" else "") + (" (normalised rewards)" if args.norm_reward else "")
-    rows["warm-started policy" + tag] = evaluate_policy(pol, eval_rooms, **kw)
+    rows[("masked warm start" if masked_imitation else "warm-started policy") + how + tag] = \
+        evaluate_policy(pol, eval_rooms, **ekw)
     then_hist, then_s = [], 0.0
     if args.then is not None:
         def show_then(it, done, st):
@@ -110,10 +121,11 @@ def main():
                      seed=args.seed)
         t1 = time.time()
         if args.then == "kickstart":
-            kl = KickstartLearner(pol, labels=args.labels, **hyper)
+            kl = KickstartLearner(pol, labels=args.labels, action_masks=masked_imitation, **hyper)
             then_hist = kickstart(col, kl, total_timesteps=steps, bc_coef=lambda i: args.bc_decay ** i,
                                   callback=show_then)
-            print(f"kickstart: fused loss minibatches {kl.fused_updates} of {kl.n_updates}")
+            print(f"kickstart: fused loss minibatches {kl.fused_updates} of {kl.n_updates}"
+                  f" (masked: {kl.masked_fused_updates})")
         elif args.action_masks:
             mcol = RolloutCollector(env, pol, n_steps=args.n_steps, reward_norm=rnorm, action_masks=True)
             ml = PPOLearner(pol, action_masks=True, **hyper)
@@ -124,7 +136,8 @@ def main():
         torch.cuda.synchronize()
         then_s = time.time() - t1
         if args.action_masks:
-            rows[f"warm start, then {args.then_iterations} x masked ppo, masked evaluation" + tag] = \
+            what = "masked warm start" if masked_imitation else "warm start"
+            rows[f"{what}, then {args.then_iterations} x masked {args.then}, masked evaluation" + tag] = \
                 evaluate_policy(pol, eval_rooms, action_masks=True, **kw)
             rows["the same policy, unmasked evaluation" + tag] = evaluate_policy(pol, eval_rooms, **kw)
         else:
@@ -133,7 +146,7 @@ def main():
     env.close()
     rows["frontier planner"] = evaluate_planner(eval_rooms, **kw)
     print(f"warm start: {len(hist)} iterations, {hist[-1]['num_timesteps']} env steps, {train_s:.1f} s "
-          f"(fused loss minibatches: {ln.fused_updates} of {ln.n_updates})")
+          f"(fused loss minibatches: {ln.fused_updates} of {ln.n_updates}, masked: {ln.masked_fused_updates})")
     print(RESULTS_HEADER)
     for label, r in rows.items():
         print(results_table_row(f"{args.eval_set}: {label}", r))
