@@ -1,9 +1,10 @@
 // head_loss.h -- the fused "head loss" of the learner, once: the skeleton that
 // vn_ppo_loss (voxnav_ppo_loss.hip), vn_bc_loss / vn_bc_loss_set
 // (voxnav_bc_loss.hip), vn_ppo_bc_loss / vn_ppo_bc_loss_set
-// (voxnav_ppo_bc_loss.hip), vn_ppo_loss_masked (voxnav_masked_loss.hip) and
-// the masked cross-entropy entries (voxnav_masked_bc_loss.hip,
-// voxnav_masked_ppo_bc_loss.hip) share; their file headers state the formulas.
+// (voxnav_ppo_bc_loss.hip), vn_ppo_loss_masked (voxnav_masked_loss.hip), the
+// masked cross-entropy entries (voxnav_masked_bc_loss.hip,
+// voxnav_masked_ppo_bc_loss.hip) and the value-clipped vn_ppo_loss[_masked]_vclip
+// (voxnav_vclip_loss.hip) share; their file headers state the formulas.
 // Common to them, with lp = log_softmax(z), p = exp(lp), H the entropy:
 //   dz_j = (the objective's policy term)_j + (ent_coef / M) p_j (lp_j + H)
 //   dv   = vf_coef 2 (v - ret) / M
@@ -33,7 +34,12 @@
 // voxnav_masked_loss.hip, BcMasked<> in masked_bc_objective.h, PpoBcMasked<> in
 // voxnav_masked_ppo_bc_loss.hip: lp_j = z_j - logsumexp_{k in S} z_k, p_j = 0 and
 // dz_j exactly 0 outside S).  Without the trait the kernel is the unmasked one,
-// instruction for instruction.
+// instruction for instruction.  In the same way, an objective that declares
+//   static constexpr bool kValueClip = true;   value_clip(s, v) -> ClippedValue
+// has the value term run on the clipped value v' (ValueClipped<> in
+// voxnav_vclip_loss.hip): the squared error is (ret - v')^2 and dv is the
+// formula's on v' where the clip passes the gradient, exactly 0 elsewhere.
+// Without it the value term is the one above.
 //
 // LDS (HeadLayout, all of it dynamic; used by the kernel's carve and by the
 // launcher's byte count): action weights [AM][F], then the waves'
@@ -97,6 +103,18 @@ template <class Obj, class = void>
 struct has_allowed : std::false_type {};
 template <class Obj>
 struct has_allowed<Obj, std::void_t<decltype(Obj::kAllowed)>> : std::bool_constant<Obj::kAllowed> {};
+
+// the objective's kValueClip trait (false when it declares none)
+template <class Obj, class = void>
+struct has_value_clip : std::false_type {};
+template <class Obj>
+struct has_value_clip<Obj, std::void_t<decltype(Obj::kValueClip)>> : std::bool_constant<Obj::kValueClip> {};
+
+// value_clip's result: the value the loss sees, and whether v takes its gradient
+struct ClippedValue {
+    float v;
+    bool pass;
+};
 
 struct HeadArgs {
     const float *hp, *hv;       // latents [M][F] (row stride ldh)
@@ -257,7 +275,15 @@ __global__ __launch_bounds__(256) void head_loss_kernel(HeadArgs g, Obj obj) {
         const float w = ok ? 1.0f : 0.0f;     // a padding pass contributes nothing
         obj.policy(blk, s, f, ok, w, inv_n);
         const float gent = g.ent_coef * inv_n * w;
-        const float dv = g.vf_coef * 2.0f * (v - ret) * inv_n * w;
+        float vl = v;                         // the value the loss sees
+        float dv;
+        if constexpr (has_value_clip<Obj>::value) {
+            const ClippedValue cv = obj.value_clip(s, v);
+            vl = cv.v;
+            dv = cv.pass ? g.vf_coef * 2.0f * (vl - ret) * inv_n * w : 0.0f;
+        } else {
+            dv = g.vf_coef * 2.0f * (v - ret) * inv_n * w;
+        }
         float4 dh[Q];
 #pragma unroll
         for (int q = 0; q < Q; ++q) dh[q] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -286,7 +312,7 @@ __global__ __launch_bounds__(256) void head_loss_kernel(HeadArgs g, Obj obj) {
                     make_float4(dv * wvv[q].x, dv * wvv[q].y, dv * wvv[q].z, dv * wvv[q].w);
             }
             if (gl == 0) {
-                st[1] += (double)((ret - v) * (ret - v));
+                st[1] += (double)((ret - vl) * (ret - vl));
                 st[2] += (double)f.ent;
                 obj.stats(s, f, st);
             }

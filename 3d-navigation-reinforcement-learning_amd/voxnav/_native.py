@@ -149,6 +149,12 @@ _SIGS = {
     "vn_ppo_loss_masked_part_floats": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, P, P]),
     "vn_ppo_loss_masked": (C.c_int, [P, P, C.c_int64, P, P, P, P, P, P, P, P, P, P, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_float, C.c_float, C.c_float, C.c_int32, P, P, P, P, P, P, P, P]),
+    "vn_ppo_loss_vclip": (C.c_int, [P, P, C.c_int64, P, P, P, P, P, P, P, P, P, P, C.c_int32, C.c_int32, C.c_int32,
+                                    C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, P, P, P, P, P, P, P, P]),
+    "vn_ppo_loss_masked_vclip": (C.c_int, [P, P, C.c_int64, P, P, P, P, P, P, P, P, P, P, P, C.c_int32, C.c_int32,
+                                           C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, P, P, P,
+                                           P, P, P, P, P]),
+    "vn_kl_gate": (C.c_int, [P, C.c_int32, C.c_double, P, P, P, P, P]),
     "vn_bc_loss_part_floats": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, P, P]),
     "vn_bc_loss": (C.c_int, [P, P, C.c_int64, P, P, P, P, P, P, P, P, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                              C.c_float, P, P, P, P, P, P, P]),

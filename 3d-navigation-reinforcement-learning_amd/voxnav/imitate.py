@@ -287,7 +287,11 @@ class BCLearner(PPOLearner):
 
     def __init__(self, policy, learning_rate: float = 3e-4, n_epochs: int = 10, batch_size: int = 64,
                  ent_coef: float = 0.0, vf_coef: float = 0.5, max_grad_norm: float = 0.5, seed: int = 0,
-                 process_group=None, labels: str = "action", action_masks: bool = False):
+                 process_group=None, labels: str = "action", action_masks: bool = False, target_kl=None,
+                 clip_range_vf=None):
+        if target_kl is not None or clip_range_vf is not None:
+            raise ValueError("BCLearner takes no target_kl or clip_range_vf: its loss has no importance ratio "
+                             "(its fifth logged value is the accuracy) and no clipped value term")
         super().__init__(policy, learning_rate=learning_rate, n_epochs=n_epochs, batch_size=batch_size,
                          ent_coef=ent_coef, vf_coef=vf_coef, max_grad_norm=max_grad_norm, seed=seed,
                          process_group=process_group, action_masks=action_masks)
@@ -436,11 +440,15 @@ class KickstartLearner(PPOLearner):
     def __init__(self, policy, learning_rate: float = 3e-4, n_epochs: int = 10, batch_size: int = 64,
                  clip_range: float = 0.2, ent_coef: float = 0.01, vf_coef: float = 0.5, max_grad_norm: float = 0.5,
                  normalize_advantage: bool = True, seed: int = 0, process_group=None, bc_coef: float = 1.0,
-                 labels: str = "action", action_masks: bool = False):
+                 labels: str = "action", action_masks: bool = False, target_kl: Optional[float] = None,
+                 clip_range_vf=None):
+        if clip_range_vf is not None:
+            raise ValueError("KickstartLearner takes no clip_range_vf: no fused PPO+BC entry point clips the "
+                             "value update")
         super().__init__(policy, learning_rate=learning_rate, n_epochs=n_epochs, batch_size=batch_size,
                          clip_range=clip_range, ent_coef=ent_coef, vf_coef=vf_coef, max_grad_norm=max_grad_norm,
                          normalize_advantage=normalize_advantage, seed=seed, process_group=process_group,
-                         action_masks=action_masks)
+                         action_masks=action_masks, target_kl=target_kl)
         # minibatches that went through learn_ops.ppo_bc_loss / ppo_bc_loss_set or, counted in
         # masked_fused_updates as well, their masked forms
         self.fused_updates = 0
@@ -517,16 +525,17 @@ class KickstartLearner(PPOLearner):
         loss.backward()
         if self.group is not None:
             self._allreduce_grads()
-        gnorm = self._clip_step()
         with torch.no_grad():
             log_ratio = log_prob - old_lp
+            approx_kl = ((torch.exp(log_ratio) - 1) - log_ratio).mean().double()
+        gnorm = self._clip_step(approx_kl)
+        with torch.no_grad():
             top = logits.max(-1, keepdim=True).values
             ar = torch.arange(A, device=logits.device).expand_as(logits)
             amax = torch.where(logits == top, ar, torch.full_like(ar, A)).min(-1).values   # ties: the lowest index
             acc = (w.double() * right_of(amax).double()).sum() / den.double()
             return torch.stack([policy_loss.detach().double(), value_loss.detach().double(),
-                                entropy_loss.detach().double(), loss.detach().double(),
-                                ((torch.exp(log_ratio) - 1) - log_ratio).mean().double(),
+                                entropy_loss.detach().double(), loss.detach().double(), approx_kl,
                                 (torch.abs(ratio - 1) > self.clip_range).double().mean(), bc.detach().double(), acc,
                                 n.double() / w.numel(), gnorm.detach().double()])
 
@@ -543,7 +552,8 @@ class KickstartLearner(PPOLearner):
         m, n_mb = self._run_epochs(buf, epoch_orders, width=10)
         return dict(policy_gradient_loss=m[0], value_loss=m[1], entropy_loss=m[2], loss=m[3], approx_kl=m[4],
                     clip_fraction=m[5], bc_loss=m[6], accuracy=m[7], labelled=m[8], grad_norm=m[9],
-                    explained_variance=self._explained_variance(buf), n_minibatches=n_mb, n_updates=self.n_updates)
+                    explained_variance=self._explained_variance(buf), n_minibatches=n_mb, n_updates=self.n_updates,
+                    early_stop=self.early_stop, epochs_run=self.epochs_run)
 
 
 def kickstart(collector: DaggerCollector, learner: KickstartLearner, total_timesteps: int,

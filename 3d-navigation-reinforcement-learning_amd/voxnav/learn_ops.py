@@ -234,7 +234,7 @@ def _head_loss(name: str, h: torch.Tensor, action_net: torch.nn.Linear, value_ne
     npart, nspart = C.c_int64(), C.c_int64()
     sizes = ("vn_bc_loss_part_floats" if name.startswith("bc_") else
              "vn_ppo_bc_loss_part_floats" if name.startswith("ppo_bc_") else
-             "vn_ppo_loss_masked_part_floats" if name == "ppo_loss_masked" else "vn_ppo_loss_part_floats")
+             "vn_ppo_loss_masked_part_floats" if name.startswith("ppo_loss_masked") else "vn_ppo_loss_part_floats")
     _native.check(getattr(lib, sizes)(M, F, A, C.byref(npart), C.byref(nspart)), sizes)
     dh = torch.empty((2, M, F), dtype=torch.float32, device=dev)
     gh = torch.empty(A * F + A + F + 1, dtype=torch.float32, device=dev)
@@ -289,6 +289,71 @@ def ppo_loss_masked(h: torch.Tensor, action_net: torch.nn.Linear, value_net: tor
                       "int32 actions / f32 values / uint8 masks",
                       (float(clip_range), float(ent_coef), float(vf_coef), int(bool(normalize_advantage))),
                       adv_words=128)
+
+
+def _check_clip_range_vf(name: str, old_values, clip_range_vf) -> float:
+    if old_values is None:
+        raise ValueError(f"{name}: old_values is required (the rollout's f32 values)")
+    c = float(clip_range_vf)
+    if not c > 0.0:                       # also NaN
+        raise ValueError(f"{name}: clip_range_vf must be > 0 (inf: no clip), got {clip_range_vf!r}")
+    return c
+
+
+def ppo_loss_vclip(h: torch.Tensor, action_net: torch.nn.Linear, value_net: torch.nn.Linear,
+                   src: Optional[torch.Tensor], actions: torch.Tensor, advantages: torch.Tensor,
+                   old_log_prob: torch.Tensor, returns: torch.Tensor, old_values: torch.Tensor, clip_range: float,
+                   clip_range_vf: float, ent_coef: float, vf_coef: float, normalize_advantage: bool):
+    """``ppo_loss`` with the value update clipped (csrc/voxnav_vclip_loss.hip, the
+    formula in include/voxnav.h vn_ppo_loss_vclip; sb3's ``clip_range_vf``):
+    ``old_values`` f32, a flat rollout buffer like ``returns`` (the values the
+    rollout stored); the value loss is on ``v`` clamped to ``old_values`` +-
+    ``clip_range_vf``, and a sample outside that range gets no value gradient.
+    ``clip_range_vf=inf`` gives ``ppo_loss``'s bits.  Arguments, outputs and
+    stats otherwise as ``ppo_loss``."""
+    c = _check_clip_range_vf("ppo_loss_vclip", old_values, clip_range_vf)
+    return _head_loss("ppo_loss_vclip", h, action_net, value_net, src,
+                      ((actions, torch.int32), (advantages, torch.float32), (old_log_prob, torch.float32),
+                       (returns, torch.float32), (old_values, torch.float32)), "int32 actions / f32 values",
+                      (float(clip_range), c, float(ent_coef), float(vf_coef), int(bool(normalize_advantage))),
+                      adv_words=128)
+
+
+def ppo_loss_masked_vclip(h: torch.Tensor, action_net: torch.nn.Linear, value_net: torch.nn.Linear,
+                          src: Optional[torch.Tensor], actions: torch.Tensor, advantages: torch.Tensor,
+                          old_log_prob: torch.Tensor, returns: torch.Tensor, action_masks: torch.Tensor,
+                          old_values: torch.Tensor, clip_range: float, clip_range_vf: float, ent_coef: float,
+                          vf_coef: float, normalize_advantage: bool):
+    """``ppo_loss_masked`` with ``ppo_loss_vclip``'s clipped value update
+    (``vn_ppo_loss_masked_vclip``)."""
+    _required_masks("ppo_loss_masked_vclip", action_masks)
+    c = _check_clip_range_vf("ppo_loss_masked_vclip", old_values, clip_range_vf)
+    return _head_loss("ppo_loss_masked_vclip", h, action_net, value_net, src,
+                      ((actions, torch.int32), (advantages, torch.float32), (old_log_prob, torch.float32),
+                       (returns, torch.float32), (action_masks, torch.uint8), (old_values, torch.float32)),
+                      "int32 actions / f32 values / uint8 masks",
+                      (float(clip_range), c, float(ent_coef), float(vf_coef), int(bool(normalize_advantage))),
+                      adv_words=128)
+
+
+def kl_gate(stats: torch.Tensor, threshold: float, stop: torch.Tensor, skip: torch.Tensor,
+            ran: Optional[torch.Tensor] = None, err: Optional[torch.Tensor] = None, kl_index: int = 4) -> None:
+    """The learner's KL gate (csrc/voxnav_trust.hip, the rule in include/voxnav.h
+    vn_kl_gate), one launch between a fused loss and ``adam_step``: ``stop``
+    (int32 word, sticky, zeroed by the caller) is set when it was 0 and
+    ``stats[kl_index]`` (f64) > ``threshold``; ``ran`` (uint8, optional) receives
+    whether it was 0 on entry -- the minibatch counts in the logs; ``skip``
+    (int32) receives ``stop`` or-ed with ``err`` (int32, optional: the row-layout
+    LSTM's error word) for ``adam_step(skip=...)``.  Nothing is read back."""
+    dev = stats.device
+    for t, dt, what in ((stats, torch.float64, "stats"), (stop, torch.int32, "stop"), (skip, torch.int32, "skip"),
+                        (ran, torch.uint8, "ran"), (err, torch.int32, "err")):
+        if t is not None and (t.dtype != dt or t.device != dev or not t.is_contiguous() or t.numel() < 1):
+            raise ValueError(f"kl_gate: {what} must be a contiguous {dt} tensor on the stats' device")
+    if not 0 <= int(kl_index) < stats.numel():
+        raise ValueError(f"kl_gate: kl_index {kl_index} outside stats [{stats.numel()}]")
+    _native.check(_native.load().vn_kl_gate(_p(stats), int(kl_index), float(threshold), _p(err), _p(stop), _p(skip), _p(ran),
+                                 _stream(dev)), "vn_kl_gate")
 
 
 def bc_loss(h: torch.Tensor, action_net: torch.nn.Linear, value_net: torch.nn.Linear, src: Optional[torch.Tensor],

@@ -44,6 +44,23 @@ where the fused loss runs, else through torch autograd of the same formula:
 logits ``masked_fill(~S, -inf)``, ``log_softmax``, the entropy with the masked
 terms zeroed (also the CPU path).
 
+sb3's three controls over how far one ``train()`` moves the policy (DESIGN.md
+10.10), all off by default:
+
+* ``target_kl``: the passes end once a minibatch's approximate KL exceeds
+  1.5 ``target_kl``; that minibatch is logged and not stepped.  On the fused
+  path the comparison runs on the device between the loss and the Adam step
+  (``learn_ops.kl_gate``, csrc/voxnav_trust.hip: the step's skip word), the
+  remaining minibatches of that epoch run and change nothing, and the host
+  reads the stop word once per epoch; elsewhere it is a host comparison and a
+  ``break``.  With a process group the ranks' mean KL decides.
+* ``clip_range_vf``: the value loss on ``v`` clamped to the rollout's value
+  +- ``clip_range_vf`` (``learn_ops.ppo_loss_vclip`` / ``ppo_loss_masked_vclip``,
+  csrc/voxnav_vclip_loss.hip; ``torch.clamp`` on the torch path).
+* ``learning_rate``, ``clip_range`` and ``clip_range_vf`` may be callables of the
+  remaining progress in [0, 1]; ``set_progress`` evaluates them, and ``learn``
+  calls it before every ``train()``.
+
 The minibatch order is drawn from ``numpy.random.default_rng(seed)``
 (sb3 uses the global numpy generator) or passed explicitly as
 ``epoch_orders`` (what the parity tests do with ``oracle/ppo_oracle.py``).
@@ -52,7 +69,7 @@ from __future__ import annotations
 
 import os
 from contextlib import nullcontext as _nullctx
-from typing import Dict, List, Optional, Sequence
+from typing import Callable, Dict, List, Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -63,20 +80,45 @@ from .lstm_seq import dual_lstm
 from .policy import ActorCriticPolicy, RecurrentActorCriticPolicy
 
 
+Schedule = Union[float, Callable[[float], float]]
+
+
+def _check_clip_range_vf(c) -> float:
+    v = float(c)
+    if not v > 0.0:                       # also NaN
+        raise ValueError(f"clip_range_vf must be > 0 (inf: no clip), got {c!r}")
+    return v
+
+
 class PPOLearner:
-    def __init__(self, policy, learning_rate: float = 3e-4, n_epochs: int = 10, batch_size: int = 64,
-                 clip_range: float = 0.2, ent_coef: float = 0.01, vf_coef: float = 0.5, max_grad_norm: float = 0.5,
-                 normalize_advantage: bool = True, seed: int = 0, process_group=None, action_masks: bool = False):
+    def __init__(self, policy, learning_rate: Schedule = 3e-4, n_epochs: int = 10, batch_size: int = 64,
+                 clip_range: Schedule = 0.2, ent_coef: float = 0.01, vf_coef: float = 0.5,
+                 max_grad_norm: float = 0.5, normalize_advantage: bool = True, seed: int = 0, process_group=None,
+                 action_masks: bool = False, target_kl: Optional[float] = None,
+                 clip_range_vf: Optional[Schedule] = None):
         if not isinstance(policy, (ActorCriticPolicy, RecurrentActorCriticPolicy)):
             raise TypeError("policy must be an ActorCriticPolicy or RecurrentActorCriticPolicy")
         if batch_size < 1 or n_epochs < 1:
             raise ValueError("batch_size and n_epochs must be >= 1")
+        if target_kl is not None and not (np.isfinite(float(target_kl)) and float(target_kl) > 0.0):
+            raise ValueError(f"target_kl must be a positive finite number or None, got {target_kl!r}")
         self.policy = policy
         self.recurrent = bool(getattr(policy, "recurrent", False))
-        self.lr = float(learning_rate)
+        # learning_rate, clip_range and clip_range_vf: floats, or callables of the remaining
+        # progress (1 at the start of training, 0 at its end: sb3's schedules), evaluated by
+        # set_progress; until its first call they hold their value at 1
+        self._schedules = {k: v for k, v in (("lr", learning_rate), ("clip_range", clip_range),
+                                             ("clip_range_vf", clip_range_vf)) if callable(v)}
+        at_start = lambda v: v(1.0) if callable(v) else v  # noqa: E731
+        self.lr = float(at_start(learning_rate))
         self.n_epochs = int(n_epochs)
         self.batch_size = int(batch_size)
-        self.clip_range = float(clip_range)
+        self.clip_range = float(at_start(clip_range))
+        self.clip_range_vf = None if clip_range_vf is None else _check_clip_range_vf(at_start(clip_range_vf))
+        # stop a train() once a minibatch's approximate KL exceeds 1.5 target_kl (sb3): that
+        # minibatch is logged and not stepped, nothing after it is stepped or logged
+        self.target_kl = None if target_kl is None else float(target_kl)
+        self._kl = None              # the running train()'s gate state (_kl_begin)
         self.ent_coef = float(ent_coef)
         self.vf_coef = float(vf_coef)
         self.max_grad_norm = float(max_grad_norm)
@@ -111,6 +153,63 @@ class PPOLearner:
         if self.recurrent:
             return [int(self.rng.integers(total)) for _ in range(self.n_epochs)]
         return [self.rng.permutation(total) for _ in range(self.n_epochs)]
+
+    def set_progress(self, progress_remaining: float) -> None:
+        """Evaluate the schedules (callable ``learning_rate`` / ``clip_range`` /
+        ``clip_range_vf``) at the remaining progress in [0, 1] -- sb3's
+        ``_update_current_progress_remaining`` + ``_update_learning_rate``; ``run_loop``
+        calls it before every ``train()``.  Float hyper-parameters are left alone."""
+        p = float(progress_remaining)
+        if not 0.0 <= p <= 1.0:
+            raise ValueError(f"progress_remaining must be in [0, 1], got {progress_remaining!r}")
+        for name, fn in self._schedules.items():
+            v = float(fn(p))
+            if name == "lr":
+                self.lr = v
+                self.optimizer.param_groups[0]["lr"] = v     # learn_ops.adam_step reads it per call
+            elif name == "clip_range":
+                self.clip_range = v
+            else:
+                self.clip_range_vf = _check_clip_range_vf(v)
+
+    # ------------------------------------------------------------ target_kl
+    def _kl_begin(self, dev) -> dict:
+        """A fresh gate state (``train()``; ``update`` outside of it makes one on first use):
+        on the GPU the device words ``stop`` (sticky) and ``skip`` of learn_ops.kl_gate and the
+        minibatches' ``ran`` bytes, elsewhere the host's flag."""
+        self._kl = dict(host_stop=False, rans=[], stop=None, skip=None)
+        if torch.device(dev).type == "cuda":
+            words = torch.zeros(2, dtype=torch.int32, device=dev)
+            self._kl.update(stop=words[0:1], skip=words[1:2])
+        return self._kl
+
+    def _kl_mean(self, kl: torch.Tensor) -> torch.Tensor:
+        """The minibatch's approximate KL as a [1] f64 tensor, with a process group the
+        ranks' mean (one scalar all-reduce), so that every rank stops at the same minibatch."""
+        kl = kl.detach().double().reshape(1)
+        if self.group is None:
+            return kl
+        import torch.distributed as dist
+        kl = kl.clone()
+        dist.all_reduce(kl, op=dist.ReduceOp.SUM, group=self.group)
+        return kl / dist.get_world_size(self.group)
+
+    def _kl_gate(self, kl: torch.Tensor, err: Optional[torch.Tensor]) -> torch.Tensor:
+        """The device gate between a fused loss and the Adam step: -> the step's skip word."""
+        st = self._kl if self._kl is not None and self._kl["stop"] is not None else self._kl_begin(kl.device)
+        ran = torch.empty(1, dtype=torch.uint8, device=kl.device)
+        learn_ops.kl_gate(self._kl_mean(kl), 1.5 * self.target_kl, st["stop"], st["skip"], ran, err, kl_index=0)
+        st["rans"].append(ran)
+        return st["skip"]
+
+    def _kl_host(self, kl: torch.Tensor) -> bool:
+        """The same rule with a host comparison (one read of the KL): True -> no step, and
+        ``update_many`` / ``train`` stop after this minibatch."""
+        st = self._kl if self._kl is not None else self._kl_begin(kl.device)
+        if float(self._kl_mean(kl)) > 1.5 * self.target_kl:      # strict; a NaN does not stop
+            st["host_stop"] = True
+            return True
+        return False
 
     def _allreduce_grads(self):
         """Average the gradients over the group (one flattened all-reduce).
@@ -341,6 +440,11 @@ class PPOLearner:
         l1 = adv * ratio
         l2 = adv * torch.clamp(ratio, 1 - self.clip_range, 1 + self.clip_range)
         policy_loss = -torch.min(l1, l2).mean()
+        if self.clip_range_vf is not None:
+            # v clamped to old +- c (include/voxnav.h vn_ppo_loss_vclip): inside the range v
+            # itself, and clamp's backward passes the gradient on the inclusive range
+            old_v = buf.values.reshape(-1)[src]
+            values = torch.clamp(values, old_v - self.clip_range_vf, old_v + self.clip_range_vf)
         value_loss = Fn.mse_loss(ret, values)
         entropy_loss = -entropy.mean()
         loss = policy_loss + self.ent_coef * entropy_loss + self.vf_coef * value_loss
@@ -348,12 +452,13 @@ class PPOLearner:
         loss.backward()
         if self.group is not None:
             self._allreduce_grads()
-        gnorm = self._clip_step()
         with torch.no_grad():
             log_ratio = log_prob - old_lp
+            approx_kl = ((torch.exp(log_ratio) - 1) - log_ratio).mean().double()
+        gnorm = self._clip_step(approx_kl)
+        with torch.no_grad():
             return torch.stack([policy_loss.detach().double(), value_loss.detach().double(),
-                                entropy_loss.detach().double(), loss.detach().double(),
-                                ((torch.exp(log_ratio) - 1) - log_ratio).mean().double(),
+                                entropy_loss.detach().double(), loss.detach().double(), approx_kl,
                                 (torch.abs(ratio - 1) > self.clip_range).double().mean(),
                                 gnorm.detach().double()])
 
@@ -362,6 +467,19 @@ class PPOLearner:
         their gradient in the fused loss kernel (learn_ops.ppo_loss), then
         ``_step_fused``."""
         pol = self.policy
+        if self.clip_range_vf is not None:
+            bufs = (buf.actions.reshape(-1), buf.advantages.reshape(-1), buf.log_probs.reshape(-1),
+                    buf.returns.reshape(-1))
+            coefs = (self.clip_range, self.clip_range_vf, self.ent_coef, self.vf_coef, norm)
+            if self.action_masks:
+                dh, grads, stats = learn_ops.ppo_loss_masked_vclip(h, pol.action_net, pol.value_net, src, *bufs,
+                                                                   buf.action_masks.reshape(-1),
+                                                                   buf.values.reshape(-1), *coefs)
+                self.masked_fused_updates += 1
+            else:
+                dh, grads, stats = learn_ops.ppo_loss_vclip(h, pol.action_net, pol.value_net, src, *bufs,
+                                                            buf.values.reshape(-1), *coefs)
+            return self._step_fused(h, dh, grads, stats)
         if self.action_masks:
             dh, grads, stats = learn_ops.ppo_loss_masked(h, pol.action_net, pol.value_net, src,
                                                          buf.actions.reshape(-1), buf.advantages.reshape(-1),
@@ -389,14 +507,18 @@ class PPOLearner:
                 prm.grad = g
         if self.group is not None:
             self._allreduce_grads()
-        gnorm = self._clip_step()
+        gnorm = self._clip_step(stats[4:5])           # approx kl (the PPO objectives' stats)
         return torch.cat([stats, gnorm.detach().double().view(1)])
 
-    def _clip_step(self) -> torch.Tensor:
+    def _clip_step(self, approx_kl: Optional[torch.Tensor] = None) -> torch.Tensor:
         """clip_grad_norm_ + Adam step.  On the GPU: the norm in two launches
         (learn_ops.grad_norm_scale) and the step in one (learn_ops.adam_step),
         the clip applied by the step as its divisor of the gradients; else
-        torch's clip and step."""
+        torch's clip and step.  ``approx_kl`` (the minibatch's, a one-element
+        tensor) with ``target_kl`` set: no step once it exceeds 1.5 target_kl --
+        decided on the device before the native Adam step (learn_ops.kl_gate,
+        no host read), by a host comparison elsewhere."""
+        gate = self.target_kl is not None and approx_kl is not None
         fused = self.optimizer.param_groups[0].get("fused")
         if fused and self.params[0].is_cuda:
             gnorm, scale = learn_ops.grad_norm_scale(self.params, self.max_grad_norm)
@@ -405,7 +527,11 @@ class PPOLearner:
                 # when an in-launch hand-off times out; the step is skipped on the
                 # device while it is set (rows_check raises after the minibatches)
                 skip = lstm_seq.rows_err_word(self.params[0].device) if self.recurrent else None
+                if gate:
+                    skip = self._kl_gate(approx_kl, skip)
                 learn_ops.adam_step(self.optimizer, scale, skip=skip)
+            elif gate and self._kl_host(approx_kl):
+                return gnorm
             else:
                 self.optimizer.grad_scale = scale
                 try:
@@ -417,6 +543,8 @@ class PPOLearner:
             err = lstm_seq.rows_err_word(self.params[0].device) if self.recurrent else None
             if err is not None and err.device.type == "cpu" and int(err.item()) != 0:
                 return gnorm                # a rank's hand-off timed out (the reduced word): no step anywhere
+            if gate and self._kl_host(approx_kl):
+                return gnorm
             self.optimizer.step()
         self.n_updates += 1
         return gnorm
@@ -427,18 +555,31 @@ class PPOLearner:
         queued, so the host read of its size does not idle the GPU.
         ``windows``: every ``idx`` is a contiguous window of the rolled
         env-major order (``train``'s minibatches), which lets whole-rollout
-        minibatches take the row-layout LSTM.  Returns the stacked logs [n, 7]."""
+        minibatches take the row-layout LSTM.  Returns the stacked logs [n, 7].
+
+        With ``target_kl`` and the host rule the loop ends with the minibatch that
+        crosses the threshold (fewer rows than ``idxs``); with the device gate every
+        minibatch runs and is returned, and the ones after the stop change nothing
+        (``train`` leaves them out of its means).  Called outside ``train``, the gate
+        starts fresh with each call."""
         idxs = list(idxs)
         if not idxs:
             return torch.zeros((0, 7), dtype=torch.float64)
         nxt = self._pack_begin(buf, idxs[0], windows) if self.recurrent else None
         n0 = self.n_updates
+        own_kl = self.target_kl is not None and self._kl is None
         logs = []
-        for i, idx in enumerate(idxs):
-            cur = nxt
-            if self.recurrent and i + 1 < len(idxs):
-                nxt = self._pack_begin(buf, idxs[i + 1], windows)
-            logs.append(self.update(buf, idx, packed=cur))
+        try:
+            for i, idx in enumerate(idxs):
+                cur = nxt
+                if self.recurrent and i + 1 < len(idxs):
+                    nxt = self._pack_begin(buf, idxs[i + 1], windows)
+                logs.append(self.update(buf, idx, packed=cur))
+                if self._kl is not None and self._kl["host_stop"]:
+                    break                           # target_kl, host rule: this minibatch is the last one logged
+        finally:
+            if own_kl:
+                self._kl = None
         if self.recurrent:
             try:
                 lstm_seq.rows_check(self.params[0].device)   # a timed-out row-layout launch raises
@@ -459,7 +600,13 @@ class PPOLearner:
         """``train()``'s passes over the buffer (this class's and its subclasses'): per
         epoch the rolled (recurrent) or permuted env-major order cut into minibatches of
         ``batch_size``, through ``update_many``.  ``width``: the length of ``update``'s log
-        vector.  -> (the logs' means over the minibatches, the minibatch count)."""
+        vector.  -> (the logs' means over the minibatches, the minibatch count).
+
+        With ``target_kl`` the passes end with the epoch in which a minibatch's approximate
+        KL exceeded 1.5 target_kl (``self.early_stop``, ``self.epochs_run``); the means and
+        the count are over the minibatches up to and including that one.  On the device
+        gate the sums and the count stay on the device (weighted by the gate's ``ran``
+        bytes) and the host reads the stop word once per epoch."""
         T, N = buf.actions.shape
         total = T * N
         dev = buf.actions.device
@@ -469,16 +616,59 @@ class PPOLearner:
         acc = torch.zeros(width, dtype=torch.float64, device=dev)
         n_mb = 0
         self.policy.train()
+        self.early_stop, self.epochs_run = False, 0
+        if self.target_kl is not None:
+            return self._run_epochs_gated(buf, orders, acc)
         for order in orders:
-            if self.recurrent:
-                perm = torch.roll(torch.arange(total, device=dev), -int(order))
-            else:
-                perm = torch.as_tensor(np.asarray(order), dtype=torch.int64, device=dev)
-            logs = self.update_many(buf, [perm[s:s + self.batch_size] for s in range(0, total, self.batch_size)],
-                                    windows=self.recurrent)
+            logs = self.update_many(buf, self._minibatches(order, total, dev), windows=self.recurrent)
             acc += logs.sum(0)
             n_mb += logs.shape[0]
+            self.epochs_run += 1
         return (acc / max(1, n_mb)).tolist(), n_mb
+
+    def _minibatches(self, order, total: int, dev) -> List[torch.Tensor]:
+        if self.recurrent:
+            perm = torch.roll(torch.arange(total, device=dev), -int(order))
+        else:
+            perm = torch.as_tensor(np.asarray(order), dtype=torch.int64, device=dev)
+        return [perm[s:s + self.batch_size] for s in range(0, total, self.batch_size)]
+
+    def _run_epochs_gated(self, buf, orders, acc: torch.Tensor):
+        """``_run_epochs`` under ``target_kl``."""
+        total = buf.actions.numel()
+        dev = buf.actions.device
+        n0 = self.n_updates
+        st = self._kl_begin(dev)
+        cnt = torch.zeros((), dtype=torch.float64, device=dev)
+        try:
+            for order in orders:
+                logs = self.update_many(buf, self._minibatches(order, total, dev), windows=self.recurrent)
+                self.epochs_run += 1
+                if st["rans"]:
+                    # the device gate: one byte per minibatch, 0 after the stop
+                    if len(st["rans"]) != logs.shape[0]:
+                        raise RuntimeError("target_kl: the minibatches of an epoch took different update paths")
+                    ran = torch.cat(st["rans"]).to(torch.float64)
+                    st["rans"] = []
+                    acc += torch.where(ran.view(-1, 1) != 0, logs, logs.new_zeros(())).sum(0)
+                    cnt += ran.sum()
+                    self.early_stop = int(st["stop"].item()) != 0      # the epoch's one host read
+                else:
+                    acc += logs.sum(0)
+                    cnt += logs.shape[0]
+                    self.early_stop = st["host_stop"]
+                if self.early_stop:
+                    break
+        finally:
+            self._kl = None
+        out = torch.cat([acc / cnt.clamp(min=1.0), cnt.view(1)]).tolist()
+        n_mb = int(round(out[-1]))
+        if self.early_stop:
+            # the crossing minibatch was logged and not stepped; the skipped steps did not
+            # advance the device step counters: the next step re-reads them
+            self.n_updates = n0 + n_mb - 1
+            self.optimizer._vn_adam_t = None
+        return out[:-1], n_mb
 
     @staticmethod
     def _explained_variance(buf) -> float:
@@ -489,12 +679,15 @@ class PPOLearner:
 
     def train(self, buf, epoch_orders: Optional[Sequence] = None) -> Dict[str, float]:
         """One ``train()`` over a collector ``RolloutBuffer`` (n_epochs passes).
-        Returns the means of sb3's logged quantities."""
+        Returns the means of sb3's logged quantities, ``n_minibatches`` (the
+        ones logged), ``n_updates`` (the steps applied so far), ``early_stop``
+        (``target_kl`` ended the passes) and ``epochs_run``."""
         self._check_masks(buf)
         m, n_mb = self._run_epochs(buf, epoch_orders)
         return dict(policy_gradient_loss=m[0], value_loss=m[1], entropy_loss=m[2], loss=m[3], approx_kl=m[4],
                     clip_fraction=m[5], grad_norm=m[6], explained_variance=self._explained_variance(buf),
-                    n_minibatches=n_mb, n_updates=self.n_updates)
+                    n_minibatches=n_mb, n_updates=self.n_updates, early_stop=self.early_stop,
+                    epochs_run=self.epochs_run)
 
 
 def _ranks_share_device(group, params) -> bool:
@@ -556,6 +749,12 @@ def run_loop(collector, learner, total_timesteps: int, callback=None, begin=None
         for cb in cbs:
             if hasattr(cb, "on_rollout_end"):
                 evals.update(cb.on_rollout_end(learner.policy, done, collector.n_steps, learner.optimizer) or {})
+        # the schedules see the progress with this rollout counted (sb3's
+        # _update_current_progress_remaining); a no-op with float hyper-parameters, and a
+        # learner without schedules need not have the method
+        set_progress = getattr(learner, "set_progress", None)
+        if set_progress is not None:
+            set_progress(max(0.0, 1.0 - done / total_timesteps))
         st = learner.train(buf)
         collector.sync_weights()
         st.update(row)

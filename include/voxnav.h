@@ -997,6 +997,34 @@ int vn_ppo_loss_masked(const float *hp, const float *hv, int64_t ldh, const floa
                        int32_t normalize_advantage, float *dhp, float *dhv, float *grad_heads, double *stats,
                        double *adv_sums, float *part, double *spart, void *stream);
 
+/* vn_ppo_loss / vn_ppo_loss_masked with the value update clipped
+ * (csrc/voxnav_vclip_loss.hip; sb3 PPO.train with clip_range_vf): old_values,
+ * indexed by src like returns, are the values the rollout stored.  With
+ * c = clip_range_vf, lo_i = old_i - c and hi_i = old_i + c formed in f32,
+ *   v'_i = min(max(v_i, lo_i), hi_i)
+ *   value loss = (1/M) sum_i (ret_i - v'_i)^2
+ *   dv_i = 2 vf_coef (v'_i - ret_i) / M   where lo_i <= v_i <= hi_i (the bounds
+ *          inclusive, as torch.clamp's backward), exactly 0 elsewhere
+ * -- in exact arithmetic sb3's old + clamp(v - old, -c, c); inside the range
+ * v' is v bit for bit, so c = +inf (accepted) gives the unclipped entry's
+ * outputs.  Everything else is the unclipped entry's: stats [6] (the value
+ * loss and the loss on v'), grad_heads, the workspaces (vn_ppo_loss_part_floats
+ * / vn_ppo_loss_masked_part_floats), the launches and the refusals, plus a NULL
+ * old_values and a clip_range_vf that is NaN or <= 0. */
+int vn_ppo_loss_vclip(const float *hp, const float *hv, int64_t ldh, const float *wa, const float *ba,
+                      const float *wv, const float *bv, const int64_t *src, const int32_t *actions,
+                      const float *advantages, const float *old_log_prob, const float *returns,
+                      const float *old_values, int32_t M, int32_t F, int32_t A, float clip_range, float clip_range_vf,
+                      float ent_coef, float vf_coef, int32_t normalize_advantage, float *dhp, float *dhv,
+                      float *grad_heads, double *stats, double *adv_sums, float *part, double *spart, void *stream);
+int vn_ppo_loss_masked_vclip(const float *hp, const float *hv, int64_t ldh, const float *wa, const float *ba,
+                             const float *wv, const float *bv, const int64_t *src, const int32_t *actions,
+                             const float *advantages, const float *old_log_prob, const float *returns,
+                             const uint8_t *mask, const float *old_values, int32_t M, int32_t F, int32_t A,
+                             float clip_range, float clip_range_vf, float ent_coef, float vf_coef,
+                             int32_t normalize_advantage, float *dhp, float *dhv, float *grad_heads, double *stats,
+                             double *adv_sums, float *part, double *spart, void *stream);
+
 /* Behaviour-cloning minibatch loss + its gradient to the MLP latents
  * (csrc/voxnav_bc_loss.hip), the counterpart of vn_ppo_loss for the DAgger warm
  * start: cross-entropy to the frontier planner's actions (vn_plan_frontier) on
@@ -1202,6 +1230,21 @@ int vn_adam_step(float *const *params, const float *const *grads, float *const *
                  float *const *steps, const int64_t *sizes, int32_t count, const float *clip_scale,
                  const int32_t *skip, float lr,
                  float beta1, float beta2, float eps, int64_t step, void *stream);
+
+/* The learner's KL gate (csrc/voxnav_trust.hip; sb3 PPO.train: approx_kl_div >
+ * 1.5 * target_kl stops the update), one stream-ordered launch between a fused
+ * loss call and vn_adam_step, all words on the device:
+ *   was = *stop;  *ran = (was == 0)                      (ran nullable)
+ *   if was == 0 and stats[kl_index] > threshold: *stop = 1   (strict; a NaN does not stop)
+ *   *skip = (*stop != 0) || (err && *err != 0)           (err nullable)
+ * stop is sticky until the caller zeroes it: the minibatch whose KL crosses
+ * the threshold is logged (ran = 1) and not stepped (skip = 1), and every later
+ * one is neither.  skip is what vn_adam_step takes as `skip`; err is the
+ * row-layout LSTM's error word.  VN_ERR_INVALID, with nothing launched: NULL
+ * stats, stop or skip; kl_index outside 0..15; a threshold that is not a
+ * positive finite number. */
+int vn_kl_gate(const double *stats, int32_t kl_index, double threshold, const int32_t *err, int32_t *stop,
+               int32_t *skip, uint8_t *ran, void *stream);
 
 /* A PPO minibatch's rows (sb3 PPO.train over the env-major flattened rollout
  * buffer): sample i has env-major id idx[i] = env * T + t; src[i] receives its

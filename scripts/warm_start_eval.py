@@ -19,7 +19,10 @@ its table row is evaluated with masks too.  --action-masks with --then kickstart
 DAgger and masked kickstart -- the warm start runs on a ``MaskedDaggerCollector`` with
 ``BCLearner(action_masks=True)``, the then-phase continues on the same collector with
 ``KickstartLearner(action_masks=True)``, and every evaluation of the policy is masked (the final weights are
-evaluated without masks as well).  Prints the per-iteration rows, the table and one JSON line.
+evaluated without masks as well).  --target-kl, --clip-range-vf, --lr-schedule linear: the
+then-phase's learner stops a train() once a minibatch's approximate KL exceeds 1.5 target_kl, clips the value
+update (--then ppo only), and lets the learning rate fall linearly to 0 over the then-phase; the then-phase's
+epochs actually run and the seconds spent in train() are printed and reported.  Prints the per-iteration rows, the table and one JSON line.
 Needs a GPU."""
 import argparse
 import json
@@ -71,9 +74,19 @@ def main():
     ap.add_argument("--action-masks", action="store_true",
                     help="--then ppo with invalid-action masking, evaluated with masks too (DESIGN.md 10.8); "
                          "--then kickstart: masked DAgger and masked kickstart throughout (DESIGN.md 10.9)")
+    ap.add_argument("--target-kl", type=float, default=None,
+                    help="the then-phase's learner: stop a train() at approx_kl > 1.5 target_kl (DESIGN.md 10.10)")
+    ap.add_argument("--clip-range-vf", type=float, default=None, help="--then ppo: clip the value update")
+    ap.add_argument("--lr-schedule", choices=["constant", "linear"], default="constant",
+                    help="linear: the then-phase's learning rate falls to 0 with the remaining progress")
     args = ap.parse_args()
     if args.action_masks and args.then is None:
         raise SystemExit("--action-masks goes with --then ppo or --then kickstart")
+    if (args.target_kl is not None or args.clip_range_vf is not None or args.lr_schedule != "constant") and \
+            args.then is None:
+        raise SystemExit("--target-kl, --clip-range-vf and --lr-schedule go with --then ppo or --then kickstart")
+    if args.clip_range_vf is not None and args.then == "kickstart":
+        raise SystemExit("--clip-range-vf goes with --then ppo (no fused PPO+BC loss clips the value update)")
     masked_imitation = args.action_masks and args.then == "kickstart"
     if not torch.cuda.is_available():
         raise SystemExit("warm_start_eval.py needs a GPU")
@@ -107,34 +120,56 @@ def main():
     tag = (" (set labels)" if args.labels == "set" else "") + (" (normalised rewards)" if args.norm_reward else "")
     rows[("masked warm start" if masked_imitation else "warm-started policy") + how + tag] = \
         evaluate_policy(pol, eval_rooms, **ekw)
-    then_hist, then_s = [], 0.0
+    then_hist, then_s, learn_s = [], 0.0, [0.0]
+
+    def timed_train(learner):
+        """learner.train with its wall time (device-synchronised) added to learn_s"""
+        train = learner.train
+
+        def run(*a, **k):
+            torch.cuda.synchronize()
+            t = time.time()
+            out = train(*a, **k)
+            torch.cuda.synchronize()
+            learn_s[0] += time.time() - t
+            return out
+
+        learner.train = run
+        return learner
+
     if args.then is not None:
         def show_then(it, done, st):
             keys = ("bc_coef", "loss", "policy_gradient_loss", "value_loss", "entropy_loss", "approx_kl", "bc_loss",
-                    "accuracy", "grad_norm", "ep_finished_rate", "ep_bumps_mean", "ep_coverage", "ret_rms_var")
+                    "accuracy", "grad_norm", "epochs_run", "n_minibatches", "ep_finished_rate", "ep_bumps_mean", "ep_coverage", "ret_rms_var")
             print(f"{args.then} iter {it:3d} steps {done:9d} " + " ".join(f"{k}={st[k]:.4g}" for k in keys if k in st),
                   flush=True)
 
         col.set_beta(0.0)
         steps = args.then_iterations * args.agents * args.n_steps
-        hyper = dict(learning_rate=args.lr, n_epochs=args.epochs, batch_size=args.batch, vf_coef=args.vf_coef,
-                     seed=args.seed)
+        lr = (lambda p: args.lr * p) if args.lr_schedule == "linear" else args.lr
+        hyper = dict(learning_rate=lr, n_epochs=args.epochs, batch_size=args.batch, vf_coef=args.vf_coef,
+                     seed=args.seed, target_kl=args.target_kl)
+        ppo_hyper = dict(hyper, clip_range_vf=args.clip_range_vf)
         t1 = time.time()
         if args.then == "kickstart":
-            kl = KickstartLearner(pol, labels=args.labels, action_masks=masked_imitation, **hyper)
+            kl = timed_train(KickstartLearner(pol, labels=args.labels, action_masks=masked_imitation, **hyper))
             then_hist = kickstart(col, kl, total_timesteps=steps, bc_coef=lambda i: args.bc_decay ** i,
                                   callback=show_then)
             print(f"kickstart: fused loss minibatches {kl.fused_updates} of {kl.n_updates}"
                   f" (masked: {kl.masked_fused_updates})")
         elif args.action_masks:
             mcol = RolloutCollector(env, pol, n_steps=args.n_steps, reward_norm=rnorm, action_masks=True)
-            ml = PPOLearner(pol, action_masks=True, **hyper)
+            ml = timed_train(PPOLearner(pol, action_masks=True, **ppo_hyper))
             then_hist = learn(mcol, ml, total_timesteps=steps, callback=show_then)
             print(f"masked ppo: fused masked loss minibatches {ml.masked_fused_updates} of {ml.n_updates}")
         else:
-            then_hist = learn(col, PPOLearner(pol, **hyper), total_timesteps=steps, callback=show_then)
+            then_hist = learn(col, timed_train(PPOLearner(pol, **ppo_hyper)), total_timesteps=steps,
+                              callback=show_then)
         torch.cuda.synchronize()
         then_s = time.time() - t1
+        print(f"{args.then}: epochs run {sum(h['epochs_run'] for h in then_hist)} of "
+              f"{args.then_iterations * args.epochs}, early stops {sum(bool(h['early_stop']) for h in then_hist)} of "
+              f"{len(then_hist)} iterations, learner {learn_s[0]:.2f} s of {then_s:.2f} s")
         if args.action_masks:
             what = "masked warm start" if masked_imitation else "warm start"
             rows[f"{what}, then {args.then_iterations} x masked {args.then}, masked evaluation" + tag] = \
@@ -151,7 +186,7 @@ def main():
     for label, r in rows.items():
         print(results_table_row(f"{args.eval_set}: {label}", r))
     print(json.dumps(dict(args=vars(args), train_seconds=train_s, history=hist, then_seconds=then_s,
-                          then_history=then_hist,
+                          then_learner_seconds=learn_s[0], then_history=then_hist,
                           table={k: {a: b for a, b in r.items() if a != "episodes"} for k, r in rows.items()})))
 
 
