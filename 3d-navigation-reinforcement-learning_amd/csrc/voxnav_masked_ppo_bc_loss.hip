@@ -26,9 +26,9 @@
 // (not normalised), bc_coef = 1 and the taken actions inside the masks the
 // gradients are vn_bc_loss_masked's (vn_bc_loss_set_masked's).
 //
-// The objective is PpoBcMasked<Bc>: PpoBc<Bc> (ppo_bc_objective.h) with the
-// mask pointer, a Sample that carries the byte, and head_loss.h's kAllowed
-// trait; the label's bits are masked_bc_objective.h's.
+// The objective is PpoBcMasked<Bc> (masked_ppo_bc_objective.h): PpoBc<Bc>
+// (ppo_bc_objective.h) with the mask pointer, a Sample that carries the byte,
+// and head_loss.h's kAllowed trait; the label's bits are masked_bc_objective.h's.
 //
 // HBM per sample: vn_ppo_bc_loss's + 1 B (the mask).
 
@@ -41,6 +41,7 @@
 #include "bc_objective.h"
 #include "head_loss.h"
 #include "masked_bc_objective.h"
+#include "masked_ppo_bc_objective.h"
 #include "ppo_bc_objective.h"
 #include "ppo_objective.h"
 #include "vn_common.h"
@@ -48,26 +49,6 @@
 using vn_detail::fail;
 
 namespace {
-
-template <class Bc>
-struct PpoBcMasked : PpoBc<Bc> {
-    using Base = PpoBc<Bc>;
-    static constexpr bool kAllowed = true;
-    const uint8_t *mask;        // [rows] bit j: action j allowed
-    struct Sample : Base::Sample {
-        unsigned mask;
-    };
-    __device__ __forceinline__ Sample gather(const typename Base::Block &b, int64_t r, int A) const {
-        Sample s;
-        static_cast<typename Base::Sample &>(s) = Base::gather(b, r, A);
-        s.mask = mask[r];
-        return s;
-    }
-    __device__ __forceinline__ unsigned allowed(const Sample &s, int A) const {
-        const unsigned taken = (unsigned)s.p.act < (unsigned)A ? 1u << s.p.act : 0u;
-        return allowed_set(s.mask, taken | label_bits(s.b, A), A);
-    }
-};
 
 // vn_ppo_bc_loss_masked (Bc = BcLabel, int32 labels) and vn_ppo_bc_loss_set_masked (BcSet, uint8 label sets)
 template <class Bc, class Label>

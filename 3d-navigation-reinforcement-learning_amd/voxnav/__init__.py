@@ -20,6 +20,7 @@ include/voxnav.h.  Public API:
   planner.FrontierExplorer / planner.evaluate_planner   the frontier-exploration baseline from the agents' belief maps
   imitate.DaggerCollector / imitate.BCLearner / imitate.warm_start   DAgger warm start from the frontier planner
   KickstartLearner / kickstart   PPO with a decaying cross-entropy to the planner's labels (imitate)
+  imitate: labels="soft", label_tau / execute="best"   distance-weighted planner labels; the policy's own sample on shortest paths
   normalize.RewardNormalizer   VecNormalize(norm_reward=True) on the rollout buffer, on the device
   checkpoint.save_reward_norm / load_reward_norm   its running statistics and returns (.npz)
   masking.action_masks   invalid-action masks from CubicEnv observations (RolloutCollector / PPOLearner action_masks=True)

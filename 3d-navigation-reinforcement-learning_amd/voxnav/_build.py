@@ -25,12 +25,13 @@ SOURCES = [CSRC / "voxnav_env.hip", CSRC / "voxnav_simple.hip", CSRC / "voxnav_s
            CSRC / "voxnav_gemm_f32.hip", CSRC / "voxnav_policy_f32.hip", CSRC / "voxnav_ppo_loss.hip",
            CSRC / "voxnav_bc_loss.hip", CSRC / "voxnav_ppo_bc_loss.hip", CSRC / "voxnav_rnorm.hip",
            CSRC / "voxnav_mask.hip", CSRC / "voxnav_masked_loss.hip", CSRC / "voxnav_masked_bc_loss.hip",
-           CSRC / "voxnav_masked_ppo_bc_loss.hip", CSRC / "voxnav_vclip_loss.hip", CSRC / "voxnav_trust.hip"]
+           CSRC / "voxnav_masked_ppo_bc_loss.hip", CSRC / "voxnav_vclip_loss.hip", CSRC / "voxnav_trust.hip",
+           CSRC / "voxnav_soft_bc_loss.hip", CSRC / "voxnav_soft_ppo_bc_loss.hip"]
 HEADERS = [INCLUDE / "voxnav.h", CSRC / "vn_error.h", CSRC / "vn_common.h", CSRC / "env_plan.h", CSRC / "env_params.h",
            CSRC / "env_core.h", CSRC / "env_state.h", CSRC / "env_route.h", CSRC / "env_planes.h", CSRC / "env_window.h", CSRC / "env_sense.h",
            CSRC / "simple_draw.h", CSRC / "simple_bits.h", CSRC / "simple_line.h", CSRC / "ret_rms.h", CSRC / "head_loss.h",
            CSRC / "ppo_objective.h", CSRC / "bc_objective.h", CSRC / "ppo_bc_objective.h",
-           CSRC / "masked_bc_objective.h"]
+           CSRC / "masked_bc_objective.h", CSRC / "masked_ppo_bc_objective.h", CSRC / "soft_bc_objective.h"]
 ARCH = os.environ.get("VOXNAV_ARCH", "gfx950")
 
 # -ffp-contract=off: the reward (f64) and obs quotients must follow the

@@ -175,7 +175,19 @@ _SIGS = {
     "vn_ppo_bc_loss_set_masked": (C.c_int, [P, P, C.c_int64, P, P, P, P, P, P, P, P, P, P, P, P, C.c_int32, C.c_int32,
                                             C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32, P, P, P,
                                             P, P, P, P, P]),
+    "vn_bc_loss_soft": (C.c_int, [P, P, C.c_int64, P, P, P, P, P, P, C.c_int64, P, P, C.c_int32, C.c_int32, C.c_int32,
+                                  C.c_float, C.c_float, C.c_float, P, P, P, P, P, P, P]),
+    "vn_bc_loss_soft_masked": (C.c_int, [P, P, C.c_int64, P, P, P, P, P, P, C.c_int64, P, P, P, C.c_int32, C.c_int32,
+                                         C.c_int32, C.c_float, C.c_float, C.c_float, P, P, P, P, P, P, P]),
+    "vn_ppo_bc_loss_soft": (C.c_int, [P, P, C.c_int64, P, P, P, P, P, P, P, P, P, P, C.c_int64, P, C.c_int32,
+                                      C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                      C.c_int32, P, P, P, P, P, P, P, P]),
+    "vn_ppo_bc_loss_soft_masked": (C.c_int, [P, P, C.c_int64, P, P, P, P, P, P, P, P, P, P, C.c_int64, P, P,
+                                             C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float, C.c_float,
+                                             C.c_float, C.c_float, C.c_int32, P, P, P, P, P, P, P, P]),
     "vn_dagger_mix": (C.c_int, [P, P, P, C.c_int32, C.c_double, C.c_uint64, C.c_uint64, C.c_int64, P, P, P, P]),
+    "vn_dagger_mix_best": (C.c_int, [P, P, P, P, C.c_int32, C.c_double, C.c_uint64, C.c_uint64, C.c_int64, P, P, P,
+                                     P, P]),
     "vn_grad_norm": (C.c_int, [P, P, C.c_int32, C.c_float, P, P, P, P]),
     "vn_adam_step": (C.c_int, [P, P, P, P, P, P, C.c_int32, P, P, C.c_float, C.c_float, C.c_float, C.c_float,
                                C.c_int64, P]),

@@ -29,6 +29,15 @@ Online Learning", AISTATS 2011):
   with the label (and, under PPO, the taken action) added -- the planner never
   labels an action the mask forbids, so the label is always in the support.
 
+* ``labels="soft"`` / ``execute="best"``: the two consumers
+  of the planner's per-action distances.  The learners' target becomes the
+  distance-weighted distribution of include/voxnav.h vn_bc_loss_soft (a
+  temperature ``label_tau``; the loss is KL(q || pi)), through
+  ``learn_ops.bc_loss_soft`` / ``ppo_bc_loss_soft`` and their masked forms; the
+  collectors execute the policy's own sample whenever it is among the shortest
+  actions (``vn_dagger_mix_best``), so the rollouts stay on the paths the
+  policy itself prefers.
+
 The policy module is the one ``PPOLearner``, ``save_checkpoint`` and
 ``evaluate_policy`` take: a warm start followed by ``ppo.learn`` needs no
 conversion.  CubicEnv variant only, rooms within the planner's 64 x 64 bound.
@@ -73,7 +82,10 @@ class DaggerBuffer(RolloutBuffer):
     A collector with ``labels="set"`` also fills ``expert_dists`` ([T, N, 6]
     int32: the planner's distance through each first action, -1 unreached, -2
     not passable) and ``expert_set`` ([T, N] uint8: bit k set where action k
-    is among the shortest; 0 where dist = -1); both are None otherwise."""
+    is among the shortest; 0 where dist = -1); both are None otherwise
+    (``labels="soft"`` fills the same two).  A collector with
+    ``execute="best"`` fills ``own_best`` ([T, N] uint8: 1 where the policy's own
+    sample was among the shortest actions of a labelled state); None otherwise."""
     expert_actions: Optional[torch.Tensor] = None
     expert_dist: Optional[torch.Tensor] = None
     label_weight: Optional[torch.Tensor] = None
@@ -81,6 +93,7 @@ class DaggerBuffer(RolloutBuffer):
     policy_actions: Optional[torch.Tensor] = None
     expert_dists: Optional[torch.Tensor] = None
     expert_set: Optional[torch.Tensor] = None
+    own_best: Optional[torch.Tensor] = None
 
 
 @dataclass
@@ -92,9 +105,25 @@ class MaskedDaggerBuffer(DaggerBuffer, MaskedRolloutBuffer):
 
 
 def _check_labels(labels) -> str:
-    if labels not in ("action", "set"):
-        raise ValueError(f"labels must be 'action' or 'set', got {labels!r}")
+    if labels not in ("action", "set", "soft"):
+        raise ValueError(f"labels must be 'action', 'set' or 'soft', got {labels!r}")
     return labels
+
+
+def _check_execute(execute, labels: str) -> str:
+    if execute not in ("expert", "best"):
+        raise ValueError(f"execute must be 'expert' or 'best', got {execute!r}")
+    if execute == "best" and labels == "action":
+        raise ValueError("execute='best' needs labels='set' or 'soft': with labels='action' the planner is not "
+                         "asked for the set of shortest actions")
+    return execute
+
+
+def _check_tau(tau) -> float:
+    v = float(tau)
+    if not (np.isfinite(v) and v > 0.0):
+        raise ValueError(f"label_tau must be finite and > 0, got {tau!r}")
+    return v
 
 
 def _check_beta(beta) -> float:
@@ -105,8 +134,16 @@ def _check_beta(beta) -> float:
 
 
 def _buffer_labels(buf, labels: str, who: str):
-    """The flat labels (``expert_set`` or ``expert_actions``) and label weights (or None) of a
-    buffer for learner ``who``; raises where the buffer does not carry them."""
+    """The flat labels (``expert_set``, ``expert_actions``, or the rows of ``expert_dists``) and
+    label weights (or None) of a buffer for learner ``who``; raises where the buffer does not
+    carry them."""
+    if labels == "soft":
+        lab = getattr(buf, "expert_dists", None)
+        if lab is None:
+            raise ValueError(f"{who}(labels='soft') needs the buffer's expert_dists (a DaggerCollector with "
+                             "labels='soft' or 'set')")
+        w = getattr(buf, "label_weight", None)
+        return lab.reshape(-1, lab.shape[-1]), (None if w is None else w.reshape(-1))
     if labels == "set":
         lab = getattr(buf, "expert_set", None)
         if lab is None:
@@ -134,12 +171,22 @@ class DaggerCollector(RolloutCollector):
     first action (one ``plan_frontier_dists`` call per step in place of
     ``plan_frontier``) and the buffer carries ``expert_dists`` and
     ``expert_set`` as well.  The executed action does not change: the
-    planner's lowest-k action with probability ``beta``."""
+    planner's lowest-k action with probability ``beta``.  ``labels="soft"``
+    is the same planner call and the same buffers (the learners read
+    ``expert_dists`` in place of ``expert_set``).
+
+    ``execute="best"`` (with ``labels="set"`` or ``"soft"``): the planner's
+    action is executed only where the policy's own sample is not among the
+    shortest actions (``vn_dagger_mix_best``, the same draw, one launch), and
+    the buffer carries ``own_best``.  At beta = 1 the agent still walks a
+    shortest path, but the policy breaks the ties, not the index rule.
+    ``execute="expert"`` (the default) is ``vn_dagger_mix``."""
 
     _masked = False      # MaskedDaggerCollector: the parent collector's masked path
 
     def __init__(self, env: BatchedGridEnv, policy, *args, expert: Optional[FrontierExplorer] = None,
-                 beta: float = 1.0, mix_seed: int = 4242, labels: str = "action", **kwargs):
+                 beta: float = 1.0, mix_seed: int = 4242, labels: str = "action", execute: str = "expert",
+                 **kwargs):
         if env.variant != _native.VN_VARIANT_CUBIC:
             raise ValueError("DaggerCollector: the frontier planner needs the CubicEnv variant")
         if kwargs.pop("action_masks", False):
@@ -153,6 +200,7 @@ class DaggerCollector(RolloutCollector):
         self.beta = _check_beta(beta)
         self.mix_seed = int(mix_seed)
         self.labels = _check_labels(labels)
+        self.execute = _check_execute(execute, self.labels)
         super().__init__(env, policy, *args, action_masks=self._masked, **kwargs)
         T, N, dev = self.n_steps, self.N, self.device
         self.expert_actions = torch.zeros((T, N), dtype=torch.int32, device=dev)
@@ -160,10 +208,12 @@ class DaggerCollector(RolloutCollector):
         self.policy_actions = torch.zeros((T, N), dtype=torch.int32, device=dev)
         self.label_weight = torch.zeros((T, N), dtype=torch.uint8, device=dev)
         self.took_expert = torch.zeros((T, N), dtype=torch.uint8, device=dev)
-        self.expert_dists = self.expert_set = None
-        if self.labels == "set":
+        self.expert_dists = self.expert_set = self.own_best = None
+        if self.labels != "action":
             self.expert_dists = torch.full((T, N, 6), -2, dtype=torch.int32, device=dev)
             self.expert_set = torch.zeros((T, N), dtype=torch.uint8, device=dev)
+        if self.execute == "best":
+            self.own_best = torch.zeros((T, N), dtype=torch.uint8, device=dev)
 
     def set_beta(self, beta: float) -> None:
         """The probability of executing the planner's action, from the next ``collect()`` on."""
@@ -171,12 +221,21 @@ class DaggerCollector(RolloutCollector):
 
     def _choose_actions(self, t: int) -> None:
         self.policy_actions[t].copy_(self.actions[t])
-        if self.labels == "set":
+        if self.labels != "action":
             self.expert.act_dists(self.env, out=FrontierDists(self.expert_actions[t], self.expert_dist[t],
                                                               self.expert_dists[t], self.expert_set[t]))
         else:
             _, dist = self.expert.act(self.env, out=self.expert_actions[t], return_dist=True)
             self.expert_dist[t].copy_(dist)
+        if self.execute == "best":
+            _native.check(self.lib.vn_dagger_mix_best(_p(self.policy_actions[t]), _p(self.expert_actions[t]),
+                                                      _p(self.expert_dist[t]), _p(self.expert_set[t]), self.N,
+                                                      C.c_double(self.beta), C.c_uint64(self.mix_seed & (2 ** 64 - 1)),
+                                                      C.c_uint64(self.t_global), self.env.agent_id_base,
+                                                      _p(self.actions[t]), _p(self.took_expert[t]),
+                                                      _p(self.label_weight[t]), _p(self.own_best[t]), self._stream()),
+                          "vn_dagger_mix_best")
+            return
         _native.check(self.lib.vn_dagger_mix(_p(self.policy_actions[t]), _p(self.expert_actions[t]),
                                              _p(self.expert_dist[t]), self.N, C.c_double(self.beta),
                                              C.c_uint64(self.mix_seed & (2 ** 64 - 1)), C.c_uint64(self.t_global),
@@ -193,7 +252,7 @@ class DaggerCollector(RolloutCollector):
                    expert_actions=self.expert_actions, expert_dist=self.expert_dist,
                    label_weight=self.label_weight, took_expert=self.took_expert,
                    policy_actions=self.policy_actions, expert_dists=self.expert_dists,
-                   expert_set=self.expert_set)
+                   expert_set=self.expert_set, own_best=self.own_best)
 
 
 class MaskedDaggerCollector(DaggerCollector):
@@ -225,16 +284,37 @@ def _allowed(masks: torch.Tensor, A: int, always: torch.Tensor) -> torch.Tensor:
 
 
 def _cross_entropy(logits: torch.Tensor, labels: torch.Tensor, w: torch.Tensor, sets: bool,
-                   masks: Optional[torch.Tensor] = None, taken: Optional[torch.Tensor] = None):
+                   masks: Optional[torch.Tensor] = None, taken: Optional[torch.Tensor] = None,
+                   tau: Optional[float] = None):
     """The torch path's cross-entropy of both learners, on the minibatch's rows.  ``labels``: the
     expert's actions, or (``sets``) their uint8 sets; ``w`` [M]: 1 where the weight labels the
     sample; ``masks`` (uint8 [M], or None): the softmax runs over S = mask | label bits of a
     labelled sample | ``taken`` (the executed actions, int64, under PPO), an empty S as full.
     -> (logits with -inf outside S, log_softmax with zeros outside S, the label's (the set's)
-    log-probability [M], w with empty sets dropped, right_of(argmax) -> the argmax is the label's)."""
+    log-probability [M], w with empty sets dropped, right_of(argmax) -> the argmax is the label's).
+    ``tau`` (labels="soft"): ``labels`` are the planner's distance rows [M, >= A] and the target is
+    the distance-weighted q of include/voxnav.h vn_bc_loss_soft; the third value is then -KL(q || pi),
+    the label bits are the actions with a positive distance, and the argmax is right where its
+    distance is the shortest."""
     A = logits.shape[-1]
     ar = torch.arange(A, device=logits.device)
-    if sets:
+    soft = tau is not None
+    if soft:
+        # in_set [M, A]: P, the actions with a positive distance; q = w / sum w, w = 1 at the
+        # shortest distance and exp(-delta / tau) elsewhere in P; ln q = -delta / tau - ln sum w
+        d = labels[:, :A].long()
+        in_set = d > 0
+        some = in_set.any(-1)
+        w = w * some.to(w.dtype)
+        dmin = torch.where(in_set, d, torch.full_like(d, 2 ** 62)).min(-1, keepdim=True).values
+        delta = torch.where(in_set, d - dmin, torch.zeros_like(d))
+        e = -delta.to(logits.dtype) / tau
+        wk = torch.where(in_set, torch.where(delta == 0, torch.ones_like(e), torch.exp(e)), torch.zeros_like(e))
+        sw = torch.where(some, wk.sum(-1), torch.ones_like(wk[:, 0])).view(-1, 1)
+        q = wk / sw
+        ln_q = torch.where(q > 0, e - torch.log(sw), torch.zeros_like(e))     # (a term whose q is 0 is 0)
+        shortest = in_set & (delta == 0)
+    elif sets:
         # in_set [M, A]: bit j of the sample's set; -log sum_{j in set} p_j = lse(z) - lse(z over the set)
         in_set = ((labels.long().view(-1, 1) >> ar) & 1).bool()
         some = in_set.any(-1)
@@ -243,7 +323,7 @@ def _cross_entropy(logits: torch.Tensor, labels: torch.Tensor, w: torch.Tensor, 
         lab = labels.long()
     S = None
     if masks is not None:
-        always = (in_set if sets else ar.view(1, A) == lab.view(-1, 1)) & (w != 0).view(-1, 1)
+        always = (in_set if sets or soft else ar.view(1, A) == lab.view(-1, 1)) & (w != 0).view(-1, 1)
         if taken is not None:
             always = always | (ar.view(1, A) == taken.view(-1, 1))
         S = _allowed(masks, A, always)
@@ -252,6 +332,9 @@ def _cross_entropy(logits: torch.Tensor, labels: torch.Tensor, w: torch.Tensor, 
     if S is not None:
         # a masked action's terms are zeros (exp(0) 0 in the entropy), and it gets no gradient
         lp_all = torch.where(S, lp_all, lp_all.new_zeros(()))
+    if soft:
+        kl = torch.where(q > 0, q * (ln_q - lp_all), torch.zeros_like(q)).sum(-1)
+        return logits, lp_all, -kl, w, lambda amax: shortest.gather(1, amax.view(-1, 1)).flatten()
     if sets:
         sel = in_set if S is None else in_set & S          # (a labelled sample's set lies in S)
         masked = logits.masked_fill(~sel, float("-inf"))
@@ -262,7 +345,35 @@ def _cross_entropy(logits: torch.Tensor, labels: torch.Tensor, w: torch.Tensor, 
     return logits, lp_all, lp, w, lambda amax: amax == lab
 
 
-class BCLearner(PPOLearner):
+class _PlannerLabels:
+    """What the two learners share about their labels: the label mode's buffer fields, and the
+    temperature of ``labels="soft"`` with its schedule."""
+
+    def _init_label_tau(self, label_tau) -> None:
+        # a float, or a callable of the remaining progress like the parent's schedules
+        # (set_progress; until its first call it holds its value at 1)
+        self._label_tau_fn = label_tau if callable(label_tau) else None
+        self.label_tau = _check_tau(label_tau(1.0) if callable(label_tau) else label_tau)
+
+    def set_progress(self, progress_remaining: float) -> None:
+        """``PPOLearner.set_progress`` plus a callable ``label_tau``."""
+        super().set_progress(progress_remaining)
+        if self._label_tau_fn is not None:
+            self.label_tau = _check_tau(self._label_tau_fn(float(progress_remaining)))
+
+    def _tau(self) -> Optional[float]:
+        return self.label_tau if self.labels == "soft" else None
+
+    def _labels(self, buf):
+        who = type(self).__name__
+        lab, w = _buffer_labels(buf, self.labels, who)
+        if self.labels == "soft" and self.policy.action_net.out_features != lab.shape[-1]:
+            raise ValueError(f"{who}(labels='soft'): the policy has {self.policy.action_net.out_features} actions, "
+                             f"expert_dists has {lab.shape[-1]} columns (the planner's first actions)")
+        return lab, w
+
+
+class BCLearner(_PlannerLabels, PPOLearner):
     """Behaviour cloning on a ``DaggerBuffer``: per minibatch
         loss = CE(labelled samples) + ent_coef * (-mean H) + vf_coef * MSE(returns, values)
     (the formula of include/voxnav.h vn_bc_loss), with the parent's
@@ -283,12 +394,21 @@ class BCLearner(PPOLearner):
     (of a labelled sample) added, an empty set counting as full (the rule of
     vn_bc_loss_masked), in ``learn_ops.bc_loss_masked`` / ``bc_loss_set_masked``
     where the fused loss runs, else through torch autograd of the same formula
-    (``PPOLearner._heads``' masked_fill / log_softmax / where)."""
+    (``PPOLearner._heads``' masked_fill / log_softmax / where).
+
+    ``labels="soft"``: the labels are the buffer's ``expert_dists`` (a
+    ``DaggerCollector(labels="soft")`` or ``"set"``), the target is the
+    distance-weighted distribution of vn_bc_loss_soft at the temperature
+    ``label_tau`` (a float, or a callable of the remaining progress evaluated
+    by ``set_progress`` like the parent's schedules), ``bc_loss`` is
+    KL(target || policy), and ``accuracy`` counts the argmax among the shortest
+    actions; through ``learn_ops.bc_loss_soft`` / ``bc_loss_soft_masked`` where
+    the fused loss runs.  The policy must have the planner's 6 actions."""
 
     def __init__(self, policy, learning_rate: float = 3e-4, n_epochs: int = 10, batch_size: int = 64,
                  ent_coef: float = 0.0, vf_coef: float = 0.5, max_grad_norm: float = 0.5, seed: int = 0,
                  process_group=None, labels: str = "action", action_masks: bool = False, target_kl=None,
-                 clip_range_vf=None):
+                 clip_range_vf=None, label_tau: Union[float, Callable[[float], float]] = 1.0):
         if target_kl is not None or clip_range_vf is not None:
             raise ValueError("BCLearner takes no target_kl or clip_range_vf: its loss has no importance ratio "
                              "(its fifth logged value is the accuracy) and no clipped value term")
@@ -299,9 +419,7 @@ class BCLearner(PPOLearner):
         # masked_fused_updates as well, their masked forms
         self.fused_updates = 0
         self.labels = _check_labels(labels)
-
-    def _labels(self, buf):
-        return _buffer_labels(buf, self.labels, type(self).__name__)
+        self._init_label_tau(label_tau)
 
     def update(self, buf, idx: torch.Tensor, packed: Optional[dict] = None) -> torch.Tensor:
         """One minibatch (env-major flat ids ``idx``): loss, backward,
@@ -332,7 +450,8 @@ class BCLearner(PPOLearner):
         w = torch.ones_like(values) if weight is None else (weight[src] != 0).to(values.dtype)
         ret = buf.returns.reshape(-1)[src]
         masks = buf.action_masks.reshape(-1)[src] if self.action_masks else None
-        logits, lp_all, lp, w, right_of = _cross_entropy(logits, labels[src], w, self.labels == "set", masks)
+        logits, lp_all, lp, w, right_of = _cross_entropy(logits, labels[src], w, self.labels == "set", masks,
+                                                         tau=self._tau())
         entropy = -(lp_all.exp() * lp_all).sum(-1)
         n = w.sum()
         den = torch.clamp(n, min=1.0)
@@ -360,16 +479,18 @@ class BCLearner(PPOLearner):
         and its gradient in the fused kernel (learn_ops.bc_loss / bc_loss_set),
         then ``PPOLearner._step_fused``."""
         pol = self.policy
+        coefs = ((self.label_tau,) if self.labels == "soft" else ()) + (self.ent_coef, self.vf_coef)
         if self.action_masks:
-            fused = learn_ops.bc_loss_set_masked if self.labels == "set" else learn_ops.bc_loss_masked
+            fused = {"set": learn_ops.bc_loss_set_masked, "soft": learn_ops.bc_loss_soft_masked,
+                     "action": learn_ops.bc_loss_masked}[self.labels]
             dh, grads, stats = fused(h, pol.action_net, pol.value_net, src, labels, weight,
-                                     buf.action_masks.reshape(-1), buf.returns.reshape(-1), self.ent_coef,
-                                     self.vf_coef)
+                                     buf.action_masks.reshape(-1), buf.returns.reshape(-1), *coefs)
             self.masked_fused_updates += 1
         else:
-            fused = learn_ops.bc_loss_set if self.labels == "set" else learn_ops.bc_loss
+            fused = {"set": learn_ops.bc_loss_set, "soft": learn_ops.bc_loss_soft,
+                     "action": learn_ops.bc_loss}[self.labels]
             dh, grads, stats = fused(h, pol.action_net, pol.value_net, src, labels, weight, buf.returns.reshape(-1),
-                                     self.ent_coef, self.vf_coef)
+                                     *coefs)
         self.fused_updates += 1
         return self._step_fused(h, dh, grads, stats)
 
@@ -386,6 +507,13 @@ class BCLearner(PPOLearner):
                     grad_norm=m[6], n_minibatches=n_mb, n_updates=self.n_updates)
 
 
+def _own_best_rate(buf) -> Dict[str, float]:
+    """``own_best_rate`` of a rollout collected with ``execute="best"``: the share of steps where
+    the policy's own sample was among the shortest actions (its stochastic on-path rate)."""
+    ob = getattr(buf, "own_best", None)
+    return {} if ob is None else {"own_best_rate": float(ob.float().mean())}
+
+
 def warm_start(collector: DaggerCollector, learner: BCLearner, total_timesteps: int,
                beta: Union[float, Callable[[int], float]] = 1.0, callback=None) -> List[Dict[str, float]]:
     """DAgger: alternate ``collector.collect()`` under ``beta`` and
@@ -399,7 +527,8 @@ def warm_start(collector: DaggerCollector, learner: BCLearner, total_timesteps: 
 
     Returns the per-iteration rows: the train dict (``BCLearner.train``),
     ``beta``, ``num_timesteps``, ``expert_share`` (the mean of
-    ``took_expert``), the Monitor and exploration keys ``ppo.learn`` reports
+    ``took_expert``), ``own_best_rate`` (the mean of ``own_best``, with a
+    collector that has ``execute="best"``), the Monitor and exploration keys ``ppo.learn`` reports
     and the evaluation's ``eval/*`` keys when one ran; with a reward
     normaliser on the collector its ``ret_rms_var`` / ``ret_rms_mean``."""
     def begin(it):
@@ -408,7 +537,7 @@ def warm_start(collector: DaggerCollector, learner: BCLearner, total_timesteps: 
         return {"beta": b}
 
     return run_loop(collector, learner, total_timesteps, callback, begin=begin,
-                    extra=lambda buf: {"expert_share": float(buf.took_expert.float().mean())})
+                    extra=lambda buf: {"expert_share": float(buf.took_expert.float().mean()), **_own_best_rate(buf)})
 
 
 def _check_bc_coef(c) -> float:
@@ -418,7 +547,7 @@ def _check_bc_coef(c) -> float:
     return v
 
 
-class KickstartLearner(PPOLearner):
+class KickstartLearner(_PlannerLabels, PPOLearner):
     """PPO with an auxiliary cross-entropy to the planner's labels on the
     policy's own rollouts (kickstarting): per minibatch
         loss = PPO's loss + bc_coef * CE(labelled samples)
@@ -435,13 +564,17 @@ class KickstartLearner(PPOLearner):
     label's bits (of a labelled sample) added, an empty set counting as full
     (the rule of vn_ppo_bc_loss_masked), in ``learn_ops.ppo_bc_loss_masked`` /
     ``ppo_bc_loss_set_masked`` where the fused loss runs, else through torch
-    autograd of the same formula."""
+    autograd of the same formula.
+
+    ``labels="soft"`` / ``label_tau`` as ``BCLearner``'s (the formula of
+    vn_ppo_bc_loss_soft, through ``learn_ops.ppo_bc_loss_soft`` /
+    ``ppo_bc_loss_soft_masked``)."""
 
     def __init__(self, policy, learning_rate: float = 3e-4, n_epochs: int = 10, batch_size: int = 64,
                  clip_range: float = 0.2, ent_coef: float = 0.01, vf_coef: float = 0.5, max_grad_norm: float = 0.5,
                  normalize_advantage: bool = True, seed: int = 0, process_group=None, bc_coef: float = 1.0,
                  labels: str = "action", action_masks: bool = False, target_kl: Optional[float] = None,
-                 clip_range_vf=None):
+                 clip_range_vf=None, label_tau: Union[float, Callable[[float], float]] = 1.0):
         if clip_range_vf is not None:
             raise ValueError("KickstartLearner takes no clip_range_vf: no fused PPO+BC entry point clips the "
                              "value update")
@@ -453,14 +586,12 @@ class KickstartLearner(PPOLearner):
         # masked_fused_updates as well, their masked forms
         self.fused_updates = 0
         self.labels = _check_labels(labels)
+        self._init_label_tau(label_tau)
         self.bc_coef = _check_bc_coef(bc_coef)
 
     def set_bc_coef(self, bc_coef: float) -> None:
         """The cross-entropy's coefficient, from the next minibatch on."""
         self.bc_coef = _check_bc_coef(bc_coef)
-
-    def _labels(self, buf):
-        return _buffer_labels(buf, self.labels, type(self).__name__)
 
     def update(self, buf, idx: torch.Tensor, packed: Optional[dict] = None) -> torch.Tensor:
         """One minibatch (env-major flat ids ``idx``).  Returns the logged
@@ -484,15 +615,17 @@ class KickstartLearner(PPOLearner):
                 if h is not None:
                     bufs = (buf.actions.reshape(-1), buf.advantages.reshape(-1), buf.log_probs.reshape(-1),
                             buf.returns.reshape(-1), labels, weight)
-                    coefs = (self.clip_range, self.ent_coef, self.vf_coef, self.bc_coef, norm)
+                    coefs = (self.clip_range, self.ent_coef, self.vf_coef, self.bc_coef,
+                             *((self.label_tau,) if self.labels == "soft" else ()), norm)
                     if self.action_masks:
-                        fused = (learn_ops.ppo_bc_loss_set_masked if self.labels == "set"
-                                 else learn_ops.ppo_bc_loss_masked)
+                        fused = {"set": learn_ops.ppo_bc_loss_set_masked, "soft": learn_ops.ppo_bc_loss_soft_masked,
+                                 "action": learn_ops.ppo_bc_loss_masked}[self.labels]
                         dh, grads, stats = fused(h, pol.action_net, pol.value_net, src, *bufs,
                                                  buf.action_masks.reshape(-1), *coefs)
                         self.masked_fused_updates += 1
                     else:
-                        fused = learn_ops.ppo_bc_loss_set if self.labels == "set" else learn_ops.ppo_bc_loss
+                        fused = {"set": learn_ops.ppo_bc_loss_set, "soft": learn_ops.ppo_bc_loss_soft,
+                                 "action": learn_ops.ppo_bc_loss}[self.labels]
                         dh, grads, stats = fused(h, pol.action_net, pol.value_net, src, *bufs, *coefs)
                     self.fused_updates += 1
                     return self._step_fused(h, dh, grads, stats)
@@ -505,7 +638,8 @@ class KickstartLearner(PPOLearner):
         taken = buf.actions.reshape(-1)[src].long()
         w = torch.ones_like(values) if weight is None else (weight[src] != 0).to(values.dtype)
         masks = buf.action_masks.reshape(-1)[src] if self.action_masks else None
-        logits, lp_all, lp, w, right_of = _cross_entropy(logits, labels[src], w, self.labels == "set", masks, taken)
+        logits, lp_all, lp, w, right_of = _cross_entropy(logits, labels[src], w, self.labels == "set", masks, taken,
+                                                         tau=self._tau())
         log_prob = lp_all.gather(1, taken.view(-1, 1)).flatten()
         entropy = -(lp_all.exp() * lp_all).sum(-1)
         adv = buf.advantages.reshape(-1)[src]
@@ -568,8 +702,9 @@ def kickstart(collector: DaggerCollector, learner: KickstartLearner, total_times
     ``PPOLearner``'s).
 
     Returns the per-iteration rows: the train dict
-    (``KickstartLearner.train``), ``bc_coef``, ``num_timesteps`` and the keys
-    ``ppo.learn`` reports."""
+    (``KickstartLearner.train``), ``bc_coef``, ``num_timesteps``,
+    ``own_best_rate`` (with a collector that has ``execute="best"``) and the
+    keys ``ppo.learn`` reports."""
     collector.set_beta(0.0)
 
     def begin(it):
@@ -577,4 +712,4 @@ def kickstart(collector: DaggerCollector, learner: KickstartLearner, total_times
         learner.set_bc_coef(c)
         return {"bc_coef": c}
 
-    return run_loop(collector, learner, total_timesteps, callback, begin=begin)
+    return run_loop(collector, learner, total_timesteps, callback, begin=begin, extra=_own_best_rate)

@@ -19,6 +19,7 @@ f32 throughout (the reference's dtype).  CUDA tensors only; the CPU path
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Optional, Tuple
 
 import torch
@@ -217,7 +218,8 @@ def _head_loss(name: str, h: torch.Tensor, action_net: torch.nn.Linear, value_ne
     """What ppo_loss, bc_loss and bc_loss_set share (csrc/head_loss.h is their one kernel): the
     checks, the workspaces, the call of ``vn_<name>`` and the views of the head gradients.
     ``buffers``: the entry point's gathered buffers as (tensor or None, dtype), in its argument
-    order; ``scalars``: its arguments between the sizes and the outputs; ``adv_words``: f64
+    order (an entry with dtype None is a ctypes scalar among them, passed as it is: the soft
+    entries' ``ldd``); ``scalars``: its arguments between the sizes and the outputs; ``adv_words``: f64
     words of vn_ppo_loss' advantage sums, passed before the partials; ``n_stats``: the entry
     point's stats words."""
     lib = _native.load()
@@ -227,7 +229,7 @@ def _head_loss(name: str, h: torch.Tensor, action_net: torch.nn.Linear, value_ne
     if h.stride(2) != 1 or h.stride(1) != F:
         raise ValueError(f"{name}: latents must be row-contiguous [2, M, F]")
     for t, dt in buffers:
-        if t is not None and (t.dtype != dt or not t.is_contiguous() or t.device != dev):
+        if dt is not None and t is not None and (t.dtype != dt or not t.is_contiguous() or t.device != dev):
             raise ValueError(f"{name}: buffers must be contiguous {what} on the latents' device")
     if src is not None and (src.dtype != torch.int64 or src.numel() != M or not src.is_contiguous()):
         raise ValueError(f"{name}: src must be [M] contiguous int64")
@@ -245,7 +247,8 @@ def _head_loss(name: str, h: torch.Tensor, action_net: torch.nn.Linear, value_ne
     wv, bv = value_net.weight.detach(), value_net.bias.detach()
     adv_sums = (_p(dbl[n_stats:n_stats + adv_words]),) if adv_words else ()
     _native.check(getattr(lib, "vn_" + name)(_p(h[0]), _p(h[1]), F, _p(wa.contiguous()), _p(ba), _p(wv.contiguous()),
-                                              _p(bv), _p(src), *[_p(t) for t, _ in buffers], M, F, A, *scalars,
+                                              _p(bv), _p(src), *[t if dt is None else _p(t) for t, dt in buffers],
+                                              M, F, A, *scalars,
                                               _p(dh[0]), _p(dh[1]), _p(gh), _p(stats), *adv_sums, _p(part),
                                               _p(dbl[n_stats + adv_words:]), _stream(dev)), "vn_" + name)
     grads = (gh[:A * F].view(A, F), gh[A * F:A * F + A], gh[A * F + A:A * F + A + F].view(1, F), gh[-1:])
@@ -497,6 +500,105 @@ def ppo_bc_loss_set_masked(h: torch.Tensor, action_net: torch.nn.Linear, value_n
     return _ppo_bc("ppo_bc_loss_set_masked", h, action_net, value_net, src, actions, advantages, old_log_prob,
                    returns, label_set, torch.uint8, weight, clip_range, ent_coef, vf_coef, bc_coef,
                    normalize_advantage, action_masks)
+
+
+def _check_tau(name: str, tau) -> float:
+    """The soft entries refuse a temperature that is not finite and > 0 before anything is launched."""
+    v = float(tau)
+    if not (math.isfinite(v) and v > 0.0):
+        raise ValueError(f"{name}: tau must be finite and > 0, got {tau!r}")
+    return v
+
+
+def _dists_rows(name: str, dists: torch.Tensor, A: int):
+    """``dists`` [rows, ldd] int32 (any leading shape flattened by the caller) -> (tensor, ldd)."""
+    if dists is None or dists.dim() != 2 or dists.shape[1] < A:
+        raise ValueError(f"{name}: dists must be [rows, ldd >= A = {A}] int32 (the planner's distance through each "
+                         "first action)")
+    return dists, C.c_int64(int(dists.shape[1]))
+
+
+def bc_loss_soft(h: torch.Tensor, action_net: torch.nn.Linear, value_net: torch.nn.Linear, src: Optional[torch.Tensor],
+                 dists: torch.Tensor, weight: Optional[torch.Tensor], returns: torch.Tensor, tau: float,
+                 ent_coef: float, vf_coef: float):
+    """``bc_loss_set`` with a distance-weighted target in place of the set
+    (csrc/voxnav_soft_bc_loss.hip, the rule in include/voxnav.h vn_bc_loss_soft):
+    ``dists`` int32 [rows, ldd >= A], the planner's distance through each first
+    action (``plan_frontier_dists``: positive = path length, -1 unreached, -2 not
+    passable), a flat rollout buffer like the others.  The target is
+    q_k = w_k / sum w over the actions with a positive distance, w_k = 1 at the
+    shortest and exp(-(d_k - d*) / tau) elsewhere; the loss is KL(q || pi), its
+    gradient p - q; a sample without a positive distance is unlabelled;
+    accuracy: the argmax is among the shortest.  ``tau`` finite and > 0.
+    Everything else -- arguments, outputs, stats -- as ``bc_loss``.  Three
+    launches."""
+    tau = _check_tau("bc_loss_soft", tau)
+    dists, ldd = _dists_rows("bc_loss_soft", dists, action_net.out_features)
+    return _head_loss("bc_loss_soft", h, action_net, value_net, src,
+                      ((dists, torch.int32), (ldd, None), (weight, torch.uint8), (returns, torch.float32)),
+                      "int32 distances / uint8 weights / f32 returns", (tau, float(ent_coef), float(vf_coef)))
+
+
+def bc_loss_soft_masked(h: torch.Tensor, action_net: torch.nn.Linear, value_net: torch.nn.Linear,
+                        src: Optional[torch.Tensor], dists: torch.Tensor, weight: Optional[torch.Tensor],
+                        action_masks: torch.Tensor, returns: torch.Tensor, tau: float, ent_coef: float,
+                        vf_coef: float):
+    """``bc_loss_soft`` with invalid-action masking (``vn_bc_loss_soft_masked``):
+    ``bc_loss_masked`` with every action of a labelled sample that has a
+    positive distance added to its allowed actions."""
+    _required_masks("bc_loss_soft_masked", action_masks)
+    tau = _check_tau("bc_loss_soft_masked", tau)
+    dists, ldd = _dists_rows("bc_loss_soft_masked", dists, action_net.out_features)
+    return _head_loss("bc_loss_soft_masked", h, action_net, value_net, src,
+                      ((dists, torch.int32), (ldd, None), (weight, torch.uint8), (action_masks, torch.uint8),
+                       (returns, torch.float32)),
+                      "int32 distances / uint8 weights / uint8 masks / f32 returns",
+                      (tau, float(ent_coef), float(vf_coef)))
+
+
+def _ppo_bc_soft(name, h, action_net, value_net, src, actions, advantages, old_log_prob, returns, dists, weight,
+                 clip_range, ent_coef, vf_coef, bc_coef, tau, normalize_advantage, action_masks=None):
+    masked = name.endswith("_masked")
+    if masked:
+        _required_masks(name, action_masks)
+    tau = _check_tau(name, tau)
+    dists, ldd = _dists_rows(name, dists, action_net.out_features)
+    return _head_loss(name, h, action_net, value_net, src,
+                      ((actions, torch.int32), (advantages, torch.float32), (old_log_prob, torch.float32),
+                       (returns, torch.float32), (dists, torch.int32), (ldd, None), (weight, torch.uint8),
+                       *(((action_masks, torch.uint8),) if masked else ())),
+                      "int32 actions / f32 values / int32 distances / uint8 weights" +
+                      (" / uint8 masks" if masked else ""),
+                      (float(clip_range), float(ent_coef), float(vf_coef), float(bc_coef), tau,
+                       int(bool(normalize_advantage))), adv_words=128, n_stats=9)
+
+
+def ppo_bc_loss_soft(h: torch.Tensor, action_net: torch.nn.Linear, value_net: torch.nn.Linear,
+                     src: Optional[torch.Tensor], actions: torch.Tensor, advantages: torch.Tensor,
+                     old_log_prob: torch.Tensor, returns: torch.Tensor, dists: torch.Tensor,
+                     weight: Optional[torch.Tensor], clip_range: float, ent_coef: float, vf_coef: float,
+                     bc_coef: float, tau: float, normalize_advantage: bool):
+    """``ppo_bc_loss`` with the distance-weighted KL of ``bc_loss_soft`` in the
+    cross-entropy's place (csrc/voxnav_soft_ppo_bc_loss.hip,
+    ``vn_ppo_bc_loss_soft``): ``dists`` int32 [rows, ldd >= A]; a sample without
+    a positive distance is unlabelled, accuracy counts the argmax among the
+    shortest actions."""
+    return _ppo_bc_soft("ppo_bc_loss_soft", h, action_net, value_net, src, actions, advantages, old_log_prob, returns,
+                        dists, weight, clip_range, ent_coef, vf_coef, bc_coef, tau, normalize_advantage)
+
+
+def ppo_bc_loss_soft_masked(h: torch.Tensor, action_net: torch.nn.Linear, value_net: torch.nn.Linear,
+                            src: Optional[torch.Tensor], actions: torch.Tensor, advantages: torch.Tensor,
+                            old_log_prob: torch.Tensor, returns: torch.Tensor, dists: torch.Tensor,
+                            weight: Optional[torch.Tensor], action_masks: torch.Tensor, clip_range: float,
+                            ent_coef: float, vf_coef: float, bc_coef: float, tau: float, normalize_advantage: bool):
+    """``ppo_bc_loss_soft`` with invalid-action masking
+    (``vn_ppo_bc_loss_soft_masked``): ``ppo_bc_loss_masked`` with every action of
+    a labelled sample that has a positive distance added to its allowed
+    actions."""
+    return _ppo_bc_soft("ppo_bc_loss_soft_masked", h, action_net, value_net, src, actions, advantages, old_log_prob,
+                        returns, dists, weight, clip_range, ent_coef, vf_coef, bc_coef, tau, normalize_advantage,
+                        action_masks)
 
 
 def grad_norm_scale(params, max_norm: float, work: Optional[torch.Tensor] = None):

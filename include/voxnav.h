@@ -1186,6 +1186,74 @@ int vn_ppo_bc_loss_set_masked(const float *hp, const float *hv, int64_t ldh, con
                               int32_t normalize_advantage, float *dhp, float *dhv, float *grad_heads, double *stats,
                               double *adv_sums, float *part, double *spart, void *stream);
 
+/* vn_bc_loss_set / vn_ppo_bc_loss_set and their masked forms with a
+ * distance-weighted target in place of the set (csrc/voxnav_soft_bc_loss.hip,
+ * csrc/voxnav_soft_ppo_bc_loss.hip).  Sample i has the planner's distances
+ * d_ik = dists[r ldd + k], k < A: dists int32 with row stride ldd >= A, the
+ * values those of vn_plan_frontier_dists (positive = the path length through
+ * first action k, -1 unreached, -2 not passable), row r through src like every
+ * other gathered buffer.  tau is finite and > 0.
+ *   P_i      = { k < A : d_ik > 0 }
+ *   labelled : P_i is not empty and the weight is nonzero (a NULL weight counts
+ *              as nonzero); n is the labelled count
+ *   d*_i     = min over P_i,   delta_ik = d_ik - d*_i
+ *   w_ik     = exactly 1 where delta_ik = 0, else expf(-delta_ik / tau)   (k in P_i); 0 outside P_i
+ *   q_ik     = w_ik / sum_k w_ik
+ *   kl_i     = sum_{k in P_i} q_ik (ln q_ik - lp_ik),  ln q_ik = -delta_ik / tau - ln sum_k w_ik,
+ *              a term whose q_ik is 0 being 0
+ *   loss     = (1/max(n,1)) sum_{i labelled} kl_i + the entropy and value terms of vn_bc_loss
+ *   dz_ij    = (w_i / max(n,1)) (p_ij - q_ij) + the entropy term of vn_bc_loss   (w_i = 1 iff labelled)
+ *   accuracy : the argmax (lowest index on ties) has delta = 0
+ * The loss is KL(q || pi), not the bare cross-entropy: the gradient is the
+ * same and its floor is 0 at every tau, so stats[0] means the same at every
+ * tau and equals vn_bc_loss's cross-entropy where P_i is a singleton.
+ * tau -> 0+ gives the uniform distribution on the shortest actions (best of
+ * vn_plan_frontier_dists): a fixed target, unlike vn_bc_loss_set's, which
+ * follows the policy.  A large tau gives the uniform distribution on P_i.  No
+ * tau gives a NaN or an inf: at 1e-30 every w with delta > 0 is 0, at 1e30
+ * every w is 1.
+ * vn_ppo_bc_loss_soft is vn_ppo_bc_loss with this q_i, ce_i = kl_i and this n
+ * (PpoBc<> composes it as it composes the other two: with bc_coef = 0 the
+ * outputs equal vn_ppo_loss's as values, with all advantages 0,
+ * normalize_advantage = 0 and bc_coef = 1 the gradients equal
+ * vn_bc_loss_soft's).  The masked forms take mask after weight and run the
+ * softmax over S_i of vn_bc_loss_masked / vn_ppo_bc_loss_masked with
+ * L_i = P_i where sample i is labelled, else 0: every action the target gives
+ * mass to counts as allowed, the KL never reads a log-probability outside the
+ * support, dz is exactly 0 outside S_i, and with every S_i full the outputs
+ * are the unmasked soft entry's bits.
+ * Outputs (stats [6] / [9]), workspaces (vn_bc_loss_part_floats /
+ * vn_ppo_bc_loss_part_floats) and launches are the _set entries': n depends on
+ * the data, so the count always runs; stream-ordered, no host
+ * synchronisation, plain stores: two calls on the same inputs give the same
+ * bits.  VN_ERR_INVALID, with nothing launched: the namesake's refusals; a
+ * NULL dists; ldd < A; tau not finite or <= 0. */
+int vn_bc_loss_soft(const float *hp, const float *hv, int64_t ldh, const float *wa, const float *ba, const float *wv,
+                    const float *bv, const int64_t *src, const int32_t *dists, int64_t ldd, const uint8_t *weight,
+                    const float *returns, int32_t M, int32_t F, int32_t A, float tau, float ent_coef, float vf_coef,
+                    float *dhp, float *dhv, float *grad_heads, double *stats, float *part, double *spart,
+                    void *stream);
+int vn_bc_loss_soft_masked(const float *hp, const float *hv, int64_t ldh, const float *wa, const float *ba,
+                           const float *wv, const float *bv, const int64_t *src, const int32_t *dists, int64_t ldd,
+                           const uint8_t *weight, const uint8_t *mask, const float *returns, int32_t M, int32_t F,
+                           int32_t A, float tau, float ent_coef, float vf_coef, float *dhp, float *dhv,
+                           float *grad_heads, double *stats, float *part, double *spart, void *stream);
+int vn_ppo_bc_loss_soft(const float *hp, const float *hv, int64_t ldh, const float *wa, const float *ba,
+                        const float *wv, const float *bv, const int64_t *src, const int32_t *actions,
+                        const float *advantages, const float *old_log_prob, const float *returns,
+                        const int32_t *dists, int64_t ldd, const uint8_t *weight, int32_t M, int32_t F, int32_t A,
+                        float clip_range, float ent_coef, float vf_coef, float bc_coef, float tau,
+                        int32_t normalize_advantage, float *dhp, float *dhv, float *grad_heads, double *stats,
+                        double *adv_sums, float *part, double *spart, void *stream);
+int vn_ppo_bc_loss_soft_masked(const float *hp, const float *hv, int64_t ldh, const float *wa, const float *ba,
+                               const float *wv, const float *bv, const int64_t *src, const int32_t *actions,
+                               const float *advantages, const float *old_log_prob, const float *returns,
+                               const int32_t *dists, int64_t ldd, const uint8_t *weight, const uint8_t *mask,
+                               int32_t M, int32_t F, int32_t A, float clip_range, float ent_coef, float vf_coef,
+                               float bc_coef, float tau, int32_t normalize_advantage, float *dhp, float *dhv,
+                               float *grad_heads, double *stats, double *adv_sums, float *part, double *spart,
+                               void *stream);
+
 /* DAgger's executed action for one collector step (csrc/voxnav_bc_loss.hip):
  * per agent i of N, with the planner's proposal expert[i] / dist[i]
  * (vn_plan_frontier) and the policy's own sample policy[i],
@@ -1202,6 +1270,27 @@ int vn_ppo_bc_loss_set_masked(const float *hp, const float *hv, int64_t ldh, con
 int vn_dagger_mix(const int32_t *policy, const int32_t *expert, const int32_t *dist, int32_t N, double beta,
                   uint64_t mix_seed, uint64_t t_global, int64_t agent_id_base, int32_t *executed, uint8_t *took_expert,
                   uint8_t *label_weight, void *stream);
+
+/* vn_dagger_mix with best-set execution (csrc/voxnav_soft_bc_loss.hip): the
+ * policy's own sample is executed whenever it is among the shortest actions.
+ * The draw is vn_dagger_mix's (u24, thr, key mix_seed, counter (global agent
+ * id, t_global | 2^63)); best uint8 [N] is vn_plan_frontier_dists' best, and
+ * there is one more output, own_best uint8 [N]:
+ *   turn            = dist[i] != -1 and u24 < thr
+ *   own_best[i]     = dist[i] != -1 and 0 <= policy[i] < 8 and bit policy[i] of best[i]
+ *   executed[i]     = (turn and not own_best[i]) ? expert[i] : policy[i]
+ *   took_expert[i]  = turn and not own_best[i]
+ *   label_weight[i] = dist[i] != -1
+ * At beta = 1 every executed action with dist != -1 lies in best: the agent
+ * walks a shortest path, and the policy breaks the ties, not the index rule.
+ * Where every best[i] is the singleton of expert[i], executed and label_weight
+ * are vn_dagger_mix's bits.  executed may be the policy array itself.  One
+ * launch, stream-ordered.  VN_ERR_INVALID, with nothing launched: a NULL
+ * pointer; N < 1; beta outside [0, 1] (a NaN included). */
+int vn_dagger_mix_best(const int32_t *policy, const int32_t *expert, const int32_t *dist, const uint8_t *best,
+                       int32_t N, double beta, uint64_t mix_seed, uint64_t t_global, int64_t agent_id_base,
+                       int32_t *executed, uint8_t *took_expert, uint8_t *label_weight, uint8_t *own_best,
+                       void *stream);
 
 /* The total 2-norm of the parameter gradients (count <= 64 f32 tensors; device
  * pointers and element counts passed by host arrays) and the divisor the

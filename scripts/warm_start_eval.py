@@ -7,7 +7,11 @@ The policy is the reference's (``--policy lstm``: RecurrentActorCriticPolicy, LS
 [256, 256, 128]; ``mlp``: ActorCriticPolicy with the same MLP).  beta falls linearly from 1 by
 --beta-step per iteration down to --beta-min.  --episodes agents per evaluation, agent i reset with
 seed + i, one deterministic episode each, L 10.  --labels set trains on the planner's set of equally
-short actions (vn_plan_frontier_dists, vn_bc_loss_set) instead of its lowest-k action.
+short actions (vn_plan_frontier_dists, vn_bc_loss_set) instead of its lowest-k action.  --labels soft
+--label-tau TAU trains on the distance-weighted target of vn_bc_loss_soft; --execute best
+(with --labels set or soft) executes the policy's own sample whenever it is among the shortest actions
+(vn_dagger_mix_best) and prints own_best_rate per iteration; with either, the warm-started policy gets a
+stochastic evaluation row (sampled actions) beside the deterministic one.
 
 --then ppo | kickstart --then-iterations K: after the warm start, K more iterations
 on the same collector at beta = 0 with a fresh learner of the reference's PPO hyperparameters --
@@ -63,8 +67,12 @@ def main():
     ap.add_argument("--episodes", type=int, default=10)
     ap.add_argument("--L", type=int, default=10)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--labels", choices=["action", "set"], default="action",
-                    help="set: the planner's set of equally short actions as the label (DESIGN.md 10.5)")
+    ap.add_argument("--labels", choices=["action", "set", "soft"], default="action",
+                    help="set: the planner's set of equally short actions as the label (DESIGN.md 10.5); "
+                         "soft: the distance-weighted target (DESIGN.md 10.11)")
+    ap.add_argument("--label-tau", type=float, default=1.0, help="--labels soft: the target's temperature")
+    ap.add_argument("--execute", choices=["expert", "best"], default="expert",
+                    help="best: the policy's own sample is executed wherever it is among the shortest actions")
     ap.add_argument("--norm-reward", action="store_true",
                     help="VecNormalize(norm_reward=True) on the rollout's rewards (DESIGN.md 10.6)")
     ap.add_argument("--then", choices=["ppo", "kickstart"], default=None,
@@ -103,13 +111,14 @@ def main():
                          device=dev)
     rnorm = RewardNormalizer(args.agents, 0.99, device=dev) if args.norm_reward else None
     col = (MaskedDaggerCollector if masked_imitation else DaggerCollector)(env, pol, n_steps=args.n_steps,
-                                                                           labels=args.labels, reward_norm=rnorm)
+                                                                           labels=args.labels, execute=args.execute,
+                                                                           reward_norm=rnorm)
     ln = BCLearner(pol, learning_rate=args.lr, n_epochs=args.epochs, batch_size=args.batch, vf_coef=args.vf_coef,
-                   seed=args.seed, labels=args.labels, action_masks=masked_imitation)
+                   seed=args.seed, labels=args.labels, action_masks=masked_imitation, label_tau=args.label_tau)
     t0 = time.time()
 
     def show(it, done, st):
-        keys = ("beta", "expert_share", "labelled", "bc_loss", "accuracy", "value_loss", "grad_norm", "ep_finished_rate",
+        keys = ("beta", "expert_share", "own_best_rate", "labelled", "bc_loss", "accuracy", "value_loss", "grad_norm", "ep_finished_rate",
                 "ep_bumps_mean", "ep_coverage", "ret_rms_var")
         print(f"iter {it:3d} steps {done:9d} " + " ".join(f"{k}={st[k]:.4g}" for k in keys if k in st), flush=True)
 
@@ -117,9 +126,13 @@ def main():
                       beta=lambda i: max(args.beta_min, 1.0 - args.beta_step * i), callback=show)
     torch.cuda.synchronize()
     train_s = time.time() - t0
-    tag = (" (set labels)" if args.labels == "set" else "") + (" (normalised rewards)" if args.norm_reward else "")
-    rows[("masked warm start" if masked_imitation else "warm-started policy") + how + tag] = \
-        evaluate_policy(pol, eval_rooms, **ekw)
+    tag = ((" (set labels)" if args.labels == "set" else f" (soft labels, tau {args.label_tau:g})"
+            if args.labels == "soft" else "") + (" (best-set execution)" if args.execute == "best" else "") +
+           (" (normalised rewards)" if args.norm_reward else ""))
+    name = ("masked warm start" if masked_imitation else "warm-started policy") + how + tag
+    rows[name] = evaluate_policy(pol, eval_rooms, **ekw)
+    if args.labels == "soft" or args.execute == "best":
+        rows[name + ", stochastic evaluation"] = evaluate_policy(pol, eval_rooms, deterministic=False, **ekw)
     then_hist, then_s, learn_s = [], 0.0, [0.0]
 
     def timed_train(learner):
@@ -152,7 +165,8 @@ def main():
         ppo_hyper = dict(hyper, clip_range_vf=args.clip_range_vf)
         t1 = time.time()
         if args.then == "kickstart":
-            kl = timed_train(KickstartLearner(pol, labels=args.labels, action_masks=masked_imitation, **hyper))
+            kl = timed_train(KickstartLearner(pol, labels=args.labels, action_masks=masked_imitation,
+                                              label_tau=args.label_tau, **hyper))
             then_hist = kickstart(col, kl, total_timesteps=steps, bc_coef=lambda i: args.bc_decay ** i,
                                   callback=show_then)
             print(f"kickstart: fused loss minibatches {kl.fused_updates} of {kl.n_updates}"
